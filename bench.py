@@ -16,9 +16,16 @@ reference simulator, default_policy, paper topology, sinusoid inference
 arrivals 6/s amp 0.6 period 300 + poisson training 0.3/s, measured on one
 CPU core.  Same algorithm, same topology, same arrival processes here.
 
-A secondary RL metric (CHSAC-AF SAC updates/sec on-device, batch 256 —
-BASELINE.md: 36.9/s on CPU) is measured OUTSIDE the timed region and
-reported inside config.
+A plain run sets up, warms up, times the steps and prints the result line.
+`--dump-outputs DIR` also writes the per-replica state left by the last timed
+step as DIR/<name>.npy; with the same arguments the inputs (Philox streams
+keyed on seed and replica id) are identical from run to run, so two builds
+can be compared array for array.
+
+`--full` adds the secondary RL metrics (CHSAC-AF SAC updates/sec on-device,
+batch 256 — BASELINE.md: 36.9/s on CPU — and RL-in-the-loop events/sec),
+measured OUTSIDE the timed region and reported inside config; without it
+those config fields are null.
 """
 import argparse
 import json
@@ -26,7 +33,7 @@ import os
 import time
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
@@ -42,9 +49,42 @@ def parse_args():
     p.add_argument("--subwave", type=int, default=64, choices=[8, 64])
     p.add_argument("--fp32-coeff", type=int, default=0,
                    help="opt-in fp32 decision-score eval in the sim kernels")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary "
+                        "measurements (CHSAC-AF SAC updates/sec and "
+                        "RL-in-the-loop throughput); a plain run skips them")
     p.add_argument("--with-rl", type=int, default=1,
-                   help="also measure CHSAC-AF SAC updates/sec (untimed region)")
-    return p.parse_args()
+                   help="with --full: measure the CHSAC-AF metrics (untimed "
+                        "region); 0 leaves them out")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the per-replica state the timed path produced "
+                        "in its last step as DIR/<name>.npy (float64)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+# Per-replica tensors the advance kernel hands back to a caller (the inputs
+# of BatchedEngine.stats() / metrics_tensors() plus the simulation clocks and
+# per-DC occupancy).  Replica-major, a few hundred KB at the default size.
+DUMP_TENSORS = ("now", "ev_count", "jobs_done", "jobs_done_inf", "sum_lat",
+                "sum_lat_inf", "sum_wait", "energy_j", "util_time", "busy",
+                "cur_freq", "n_running", "p_active", "jid_ctr", "rng_ctr")
+
+
+def dump_outputs(eng, out_dir, rank, world):
+    """Write the engine's per-replica outputs as float64 .npy files.  Counters
+    stay far below 2**53, so the conversion is exact.  With several ranks
+    each writes its own shard as <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name in DUMP_TENSORS:
+        arr = eng.t[name].detach().cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def measure_rl_steps_per_sec(device, n_updates=200, batch=256):
@@ -164,7 +204,7 @@ def main():
 
     if args.algo == "chsac_af":
         raise SystemExit("chsac_af is measured by the RL-in-the-loop metric "
-                         "(rl_loop_events_per_sec, reported with --with-rl 1);"
+                         "(rl_loop_events_per_sec, reported with --full);"
                          " the raw step loop would bypass training/ingest")
     sc = paper_scenario()
     inf, trn = build_arrivals()  # sinusoid 6/s amp .6 period 300; poisson 0.3/s
@@ -212,9 +252,12 @@ def main():
 
     value = events / elapsed
 
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
+
     rl_steps_s = None
     rl_loop_ev_s = rl_loop_up_s = None
-    if args.with_rl and rank == 0:
+    if args.full and args.with_rl and rank == 0:
         rl_steps_s = measure_rl_steps_per_sec(device)
         rl_loop_ev_s, rl_loop_up_s = measure_rl_loop(device)
 

@@ -34,6 +34,19 @@ def test_algo_choices_match_reference():
         run_sim.parse_args(["--algo", "nope"])
 
 
+def test_bench_flag_surface():
+    """A plain bench run is lean by default; --full and --dump-outputs are
+    opt-in, and --steps must name a real number of timed steps."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_out_dir_rule():
     # bare name -> algo subdir; path with separator -> as-is
     assert run_sim.resolve_out_dir("logs", "bandit") == os.path.join("logs", "bandit")

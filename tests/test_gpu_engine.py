@@ -277,6 +277,44 @@ def test_bench_contract():
 
 
 @needs_gpu
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's per-replica state as
+    float64 .npy; --steps sets the timed step count; two runs with the same
+    arguments see identical inputs and so produce identical arrays; a plain
+    run leaves the --full metrics out."""
+    R, E, K, W = 512, 200, 3, 1
+    outs = []
+    for tag in ("a", "b"):
+        d = str(tmp_path / tag)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"),
+                            "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                            "--replicas-per-gpu", str(R),
+                            "--events-per-step", str(E), "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=300, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
+        res = json.loads(line)
+        assert res["steps"] == K and res["ms_per_step"] > 0
+        # value is events / elapsed and ms_per_step is elapsed / steps
+        assert res["value"] * res["ms_per_step"] * 1e-3 * K == \
+            pytest.approx(R * E * K, rel=1e-9)
+        assert res["config"]["rl_train_steps_per_sec"] is None
+        assert res["config"]["rl_loop_events_per_sec"] is None
+        outs.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = outs
+    assert set(a) == set(b) and {"ev_count.npy", "energy_j.npy", "now.npy",
+                                 "jobs_done.npy", "sum_lat.npy"} <= set(a)
+    for f in a:
+        assert a[f].dtype == np.float64 and a[f].shape[0] == R, f
+        assert np.array_equal(a[f], b[f]), f"{f} differs between runs"
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    # every replica ran exactly (warmup + steps) launches of E events
+    assert (a["ev_count.npy"] == E * (K + W)).all()
+    assert (a["energy_j.npy"].sum(axis=1) > 0).all()
+    assert (a["jobs_done.npy"] > 0).all()
+
+
+@needs_gpu
 def test_chsac_batched_runs_and_trains(tmp_path):
     """CHSAC-AF on the batched engine: replicas pause at decision points, the
     host serves batched policy actions, transitions flow into replay, SAC
