@@ -13,9 +13,11 @@
 //
 // Execution discipline: control flow is wave-uniform — every lane computes
 // the same scalar values redundantly; global-memory writes are guarded to
-// lane 0; cooperative phases (scans/argmins) use lane-strided reads + shfl
-// reductions.  Replicas are independent, so kernels need no inter-workgroup
-// communication; multi-GPU scaling shards replicas per rank
+// lane 0; cooperative phases (scans/argmins) use lane-strided reads + the
+// subgroup reductions of sim_models.hpp (64-lane build: DPP on the VALU with
+// the result in SGPRs, so the event dispatch is scalar branches; 8-lane
+// build: shfl_xor butterflies).  Replicas are independent, so kernels need
+// no inter-workgroup communication; multi-GPU scaling shards replicas per rank
 // (parallel/sharding.py) with RCCL used only for metric reductions.
 //
 // Event semantics mirror the scalar engines (engine/oracle.py ==
@@ -272,12 +274,7 @@ struct EngineDesc {
 };
 
 // ---------------- wave helpers ----------------
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int off = SUBW / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
+// (the subgroup reductions live in sim_models.hpp)
 __device__ __forceinline__ void store_fence() {
   // make lane-0 stores (global AND LDS) visible to this wave's subsequent
   // loads: full hardware wait + compiler reordering barrier
@@ -339,16 +336,44 @@ struct Ctx {
   PhiloxState rng;
   double now;       // last processed event time (or -1)
   double t_first;   // first event time (-1 until known)
+  // lane d < n_dc keeps DC d's capacity and per-idle-GPU power (already
+  // resolved to power_gating ? p_sleep : p_idle) for the kernel's lifetime:
+  // the per-event accrual reads no scenario table
+  int my_total;
+  double my_pidle;
 
-  __device__ const double* pc3(int d, int jt) const { return &S->pc[(d * 2 + jt) * 3]; }
-  __device__ const double* lc3(int d, int jt) const { return &S->lc[(d * 2 + jt) * 3]; }
+  // launch-invariant tables (sim_models.hpp: scalar loads in the 64-lane
+  // build when the index is wave-uniform)
+  __device__ kc_f64 pc3(int d, int jt) const {
+    return launch_const(S->pc) + (d * 2 + jt) * 3;
+  }
+  __device__ kc_f64 lc3(int d, int jt) const {
+    return launch_const(S->lc) + (d * 2 + jt) * 3;
+  }
+  __device__ kc_f64 freq_levels() const { return launch_const(S->freq_levels); }
+  __device__ int slot_off(int d) const { return launch_const(S->slot_off)[d]; }
+  __device__ int slot_dc(int slot) const {
+    return launch_const(S->slot_dc)[slot];
+  }
+  __device__ int total_gpus(int d) const {
+    return launch_const(S->total_gpus)[d];
+  }
   __device__ int free_gpus(int d) const {
-    return S->total_gpus[d] - hs->busy[d];
+    return total_gpus(d) - hs->busy[d];
+  }
+  __device__ double idle_gpu_power(int d) const {
+    return launch_const(S->power_gating)[d] ? launch_const(S->p_sleep)[d]
+                                            : launch_const(S->p_idle)[d];
   }
   __device__ double dc_power(int d) const {
     int idle = free_gpus(d);
-    double pi = S->power_gating[d] ? S->p_sleep[d] : S->p_idle[d];
+    double pi = idle_gpu_power(d);
     return hs->p_active[d] + idle * pi;
+  }
+  // lane's own DC, from the registers (lane < n_dc)
+  __device__ double my_dc_power() const {
+    int idle = my_total - hs->busy[lane];
+    return hs->p_active[lane] + idle * my_pidle;
   }
   __device__ double price_kwh(double t) const {
     int h = static_cast<int>(fmod(t, 86400.0) / 3600.0);
@@ -359,7 +384,7 @@ struct Ctx {
 // recompute a DC's cached min finish (wave-cooperative)
 __device__ void rescan_dc_min(Ctx& c, int d) {
   const EngineDesc& S = *c.S;
-  int lo = S.slot_off[d], hi = S.slot_off[d + 1];
+  int lo = c.slot_off(d), hi = c.slot_off(d + 1);
   double v = D_INF;
   int slot = -1;
   for (int k = lo + c.lane; k < hi; k += SUBW) {
@@ -368,7 +393,7 @@ __device__ void rescan_dc_min(Ctx& c, int d) {
   }
   int wl;
   double best = wave_argmin_f64(v, wl);
-  slot = __shfl(slot, wl, 64);
+  slot = sub_bcast_i32(slot, wl);
   if (c.lane == 0) {
     c.hs->dc_minf[d] = best;
     c.hs->dc_mins[d] = best < D_INF ? slot : -1;
@@ -377,25 +402,23 @@ __device__ void rescan_dc_min(Ctx& c, int d) {
 }
 
 // start a job on DC d with (n, f); assumes free >= 1; wave-cooperative.
-__device__ void start_job(Ctx& c, int d, int jt, double size, float netlat,
+// Keeps the DC's cached min finish exact incrementally; returns true when the
+// new finish time TIES the cached minimum — the one case where only a full
+// rescan_dc_min reproduces the scan's slot tie-break.
+__device__ bool start_job(Ctx& c, int d, int jt, double size, float netlat,
                           int jid, int ing, int n, double f, double now) {
   const EngineDesc& S = *c.S;
   int64_t base = (int64_t)c.r * S.total_slots;
-  int lo = S.slot_off[d], hi = S.slot_off[d + 1];
+  int lo = c.slot_off(d), hi = c.slot_off(d + 1);
   // find first empty slot (finish == INF <=> s_gpus == 0), from the LDS mirror
-  int cand = INT_MAX;
-  for (int k = lo + c.lane; k < hi; k += SUBW) {
-    if (c.l_fin[k] >= D_INF) { cand = k; break; }
-  }
-#pragma unroll
-  for (int off = SUBW / 2; off > 0; off >>= 1)
-    cand = min(cand, __shfl_xor(cand, off, 64));
+  int cand = sub_first_empty(c.l_fin, lo, hi);
   if (cand == INT_MAX) {  // cannot happen if capacities == total_gpus
     if (c.lane == 0) atomicOr(&S.err[c.r], ERR_SLOT_OVF);
-    return;
+    return false;
   }
   double T = d_unit_time(n, f, c.lc3(d, jt));
   double finish = now + (double)size * T;
+  double minf = c.hs->dc_minf[d];
   if (c.lane == 0) {
     c.l_fin[cand] = finish;
     SRec* sr = &S.s_rec[base + cand];
@@ -416,12 +439,13 @@ __device__ void start_job(Ctx& c, int d, int jt, double size, float netlat,
     c.hs->n_running[d] += 1;
     c.hs->p_active[d] += d_job_power(n, f, c.pc3(d, jt));
     c.hs->sum_tpt[d] += 1.0 / T;
-    if (finish < c.hs->dc_minf[d]) {
+    if (finish < minf) {
       c.hs->dc_minf[d] = finish;
       c.hs->dc_mins[d] = cand;
     }
   }
   store_fence();
+  return finish == minf;
 }
 
 // heuristic allocator (policy.py:16-41 semantics); mutates cur_freq; returns g
@@ -435,7 +459,7 @@ __device__ int heuristic_alloc(Ctx& c, int d, int jt) {
     if (jt == 0) nf = S.dvfs_high;
     else {
       int qi = c.hs->q_len[d * 2 + 0];
-      nf = fmax(cf, qi > 0 ? S.dvfs_high : S.default_freq[d]);
+      nf = fmax(cf, qi > 0 ? S.dvfs_high : launch_const(S.default_freq)[d]);
     }
   } else {
     if (jt == 0) nf = S.dvfs_high;
@@ -457,9 +481,9 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
   int free = c.free_gpus(d);
   if (ALGO == A_JOINT_NF) {
     GridPick g = S.fp32_score
-        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                S.n_freq, S.max_gpj, 0, 0.0, 0.0, false, 0.0)
-        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                            S.n_freq, S.max_gpj, 0, 0.0, 0.0, false, 0.0);
     n_out = g.n; f_out = g.f;
   } else if (ALGO == A_BANDIT) {
@@ -486,9 +510,9 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
     int obj = price > 0.0 ? 2 : 1;
     double ci = price > 0.0 ? 0.0 : S.carbon[d];
     GridPick g = S.fp32_score
-        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                S.n_freq, S.max_gpj, obj, ci, price, false, 0.0)
-        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                            S.n_freq, S.max_gpj, obj, ci, price, false, 0.0);
     n_out = g.n; f_out = g.f;
   } else if (ALGO == A_DEBUG) {
@@ -496,8 +520,8 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
     f_out = S.fixed_freq > 0 ? S.fixed_freq
             : (S.fp32_score
                ? wave_energy_freq_f32(c.pc3(d, jt), c.lc3(d, jt),
-                                      S.freq_levels, S.n_freq, S.num_fixed)
-               : wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+                                      c.freq_levels(), S.n_freq, S.num_fixed)
+               : wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                   S.n_freq, S.num_fixed));
   } else {  // heuristic family
     n_out = heuristic_alloc(c, d, jt);
@@ -586,10 +610,13 @@ __device__ bool queue_pop(Ctx& c, int d, int jt, double& size, float& netlat,
   return true;
 }
 
-// drain queues after a completion (inference first; reference :839-927)
+// drain queues after a completion (inference first; reference :839-927);
+// returns true if any started job tied the DC's cached min finish (see
+// start_job) so the caller must rescan
 template <int ALGO>
-__device__ void drain_queues(Ctx& c, int d, double now) {
+__device__ bool drain_queues(Ctx& c, int d, double now) {
   const EngineDesc& S = *c.S;
+  bool tie = false;
   while (c.free_gpus(d) > 0) {
     double size, enq;
     float netlat;
@@ -604,10 +631,10 @@ __device__ void drain_queues(Ctx& c, int d, double now) {
       // carbon_cost (simulator_paper_multi.py:909-920), unlike its admission
       // path which prefers cost when a price is set (:622-645)
       GridPick g = S.fp32_score
-          ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+          ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                  S.n_freq, S.max_gpj, 1, S.carbon[d], 0.0,
                                  false, 0.0)
-          : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+          : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                              S.n_freq, S.max_gpj, 1, S.carbon[d], 0.0,
                              false, 0.0);
       n = g.n; f = g.f;
@@ -620,9 +647,10 @@ __device__ void drain_queues(Ctx& c, int d, double now) {
       f = c.hs->cur_freq[d];
     }
     n = max(1, min(n, c.free_gpus(d)));
-    start_job(c, d, jt, size, netlat, jid, ing, n, f, now);
+    tie |= start_job(c, d, jt, size, netlat, jid, ing, n, f, now);
     if (c.lane == 0) c.hs->sum_wait += fmax(0.0, now - enq);
   }
+  return tie;
 }
 
 // accrue energy + util across DCs to time t (lanes 0..n_dc-1)
@@ -635,7 +663,7 @@ __device__ void accrue_to(Ctx& c, double t) {
     } else {
       double dt = fmax(0.0, t - last);
       c.hs->util_time[c.lane] += c.hs->busy[c.lane] * dt;
-      c.hs->energy[c.lane] += c.dc_power(c.lane) * dt;
+      c.hs->energy[c.lane] += c.my_dc_power() * dt;
     }
   }
   lds_fence();
@@ -999,7 +1027,7 @@ __device__ int rl_min_n_for_sla(Ctx& c, int d, int jt, double size, double f) {
 // reference jobs never carry deadlines — Job.deadline is always None)
 __device__ double rl_energy_freq(Ctx& c, int d, int jt, int n) {
   const EngineDesc& S = *c.S;
-  return wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), S.freq_levels,
+  return wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                           S.n_freq, n);
 }
 
@@ -1109,13 +1137,7 @@ __device__ void rl_start_job(Ctx& c, int d, int jt, double size, float netlat,
   const EngineDesc& S = *c.S;
   int64_t base = (int64_t)c.r * S.total_slots;
   int lo = S.slot_off[d], hi = S.slot_off[d + 1];
-  int cand = INT_MAX;
-  for (int k = lo + c.lane; k < hi; k += SUBW) {
-    if (c.l_fin[k] >= D_INF) { cand = k; break; }
-  }
-#pragma unroll
-  for (int off = SUBW / 2; off > 0; off >>= 1)
-    cand = min(cand, __shfl_xor(cand, off, 64));
+  int cand = sub_first_empty(c.l_fin, lo, hi);
   if (cand == INT_MAX) {
     if (c.lane == 0) atomicOr(&S.err[c.r], ERR_SLOT_OVF);
     return;
@@ -1319,13 +1341,7 @@ __device__ void rl_do_arrival(Ctx& c, double now, int jt, int ing,
   double lnet = S.wan_lat[ing * S.n_dc + d_sel];
   double bw = S.wan_bw[ing * S.n_dc + d_sel];
   double xfer = bw > 0.0 ? S.payload_gb[jt] / bw : 0.0;
-  int cand = INT_MAX;
-  for (int k = c.lane; k < S.tcap; k += SUBW) {
-    if (c.l_xt[k] >= D_INF) { cand = k; break; }
-  }
-#pragma unroll
-  for (int off = SUBW / 2; off > 0; off >>= 1)
-    cand = min(cand, __shfl_xor(cand, off, 64));
+  int cand = sub_first_empty(c.l_xt, 0, S.tcap);
   if (cand == INT_MAX) {
     if (c.lane == 0) atomicOr(&S.err[c.r], ERR_XFER_OVF);
     return;
@@ -1435,7 +1451,9 @@ __global__ void __launch_bounds__(THREADS_PER_BLOCK)
 advance_kernel(EngineDesc S, double t_target, long long max_ev) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
-  int slot_id = (blockIdx.x * blockDim.x + threadIdx.x) / SUBW;
+  // (64-lane build: the replica index is wave-uniform; say so, so that
+  // everything indexed by it is scalar address arithmetic)
+  int slot_id = sub_uniform_i32((blockIdx.x * blockDim.x + threadIdx.x) / SUBW);
   int lane = threadIdx.x & (SUBW - 1);
   if (slot_id >= S.n_rep) return;
 
@@ -1450,6 +1468,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
       S.req_flag[c.r] != REQ_READY)
     return;
   c.now = S.now[c.r];
+  {
+    bool own = lane < S.n_dc;
+    c.my_total = own ? S.total_gpus[lane] : 0;
+    c.my_pidle = own ? (S.power_gating[lane] ? S.p_sleep[lane]
+                                             : S.p_idle[lane]) : 0.0;
+  }
   c.rng.key = S.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(S.rep_id_offset + c.r));
   c.rng.ctr = S.rng_ctr[c.r];
 
@@ -1610,30 +1634,55 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
     // per-lane candidate: value + kind/idx
     double v = D_INF;
     int kind = -1, idx = -1;
-    // arrival streams (strided)
-    for (int k = lane; k < NS; k += SUBW) {
-      double t = c.hs->arr_next[k];
-      if (t < v) { v = t; kind = 0; idx = k; }
+    if (SUBW == 64) {
+      // NS <= 16 and n_dc <= 8 fit one pass, and so does the first 64 of the
+      // transfer mirror: issue all the LDS reads unconditionally (index
+      // clamped; out-of-range lanes are masked in the selects below) so they
+      // go out back to back under one wait, then pick in the same source
+      // order as the strided scans
+      double ta = c.hs->arr_next[max(0, min(lane, NS - 1))];
+      double tl = c.hs->next_log;
+      int kd = max(0, min(lane, S.n_dc - 1));
+      double td = c.hs->dc_minf[kd];
+      int sd = c.hs->dc_mins[kd];
+      double tx = c.l_xt[max(0, min(lane, S.tcap - 1))];
+      if ((lane < NS) & (ta < v)) { v = ta; kind = 0; idx = lane; }
+      if ((lane == 0) & (tl < v)) { v = tl; kind = 3; idx = 0; }
+      if ((lane < S.n_dc) & (td < v)) { v = td; kind = 2; idx = sd; }
+      if ((lane < S.tcap) & (tx < v)) { v = tx; kind = 1; idx = lane; }
+      // larger tcap: the rest of the mirror, strided
+      for (int k = lane + 64; k < S.tcap; k += 64) {
+        double t = c.l_xt[k];
+        if (t < v) { v = t; kind = 1; idx = k; }
+      }
+    } else {
+      // arrival streams (strided)
+      for (int k = lane; k < NS; k += SUBW) {
+        double t = c.hs->arr_next[k];
+        if (t < v) { v = t; kind = 0; idx = k; }
+      }
+      // log tick (one candidate)
+      if (lane == 0) {
+        double t = c.hs->next_log;
+        if (t < v) { v = t; kind = 3; idx = 0; }
+      }
+      // dc min finishes (strided; n_dc <= 8 <= SUBW so one pass)
+      for (int k = lane; k < S.n_dc; k += SUBW) {
+        double t = c.hs->dc_minf[k];
+        if (t < v) { v = t; kind = 2; idx = c.hs->dc_mins[k]; }
+      }
+      // transfers (strided over the mirror)
+      for (int k = lane; k < S.tcap; k += SUBW) {
+        double t = c.l_xt[k];
+        if (t < v) { v = t; kind = 1; idx = k; }
+      }
     }
-    // log tick (one candidate)
-    if (lane == 0) {
-      double t = c.hs->next_log;
-      if (t < v) { v = t; kind = 3; idx = 0; }
-    }
-    // dc min finishes (strided; n_dc <= 8 <= SUBW so one pass)
-    for (int k = lane; k < S.n_dc; k += SUBW) {
-      double t = c.hs->dc_minf[k];
-      if (t < v) { v = t; kind = 2; idx = c.hs->dc_mins[k]; }
-    }
-    // transfers (strided over the mirror)
-    for (int k = lane; k < S.tcap; k += SUBW) {
-      double t = c.l_xt[k];
-      if (t < v) { v = t; kind = 1; idx = k; }
-    }
+    // 64-lane build: t_min, kind and idx come back in SGPRs, so the
+    // dispatch below is scalar branches
     int wl;
     double t_min = wave_argmin_f64(v, wl);
-    kind = __shfl(kind, wl, 64);
-    idx = __shfl(idx, wl, 64);
+    kind = sub_bcast_i32(kind, wl);
+    idx = sub_bcast_i32(idx, wl);
 
     if (t_min > S.end_time) {
       // ---- end of simulation for this replica: final flush ----
@@ -1744,8 +1793,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
             int d = lane >> 3;
             int n = (lane & 7) + 1;
             if (d < S.n_dc && n <= S.max_gpj) {
-              const double* pcf = c.pc3(d, jt);
-              const double* tcf = c.lc3(d, jt);
+              kc_f64 pcf = c.pc3(d, jt);
+              kc_f64 tcf = c.lc3(d, jt);
               double best = D_INF;
               for (int q = 0; q < S.n_freq; ++q) {
                 double f = S.freq_levels[q];
@@ -1772,8 +1821,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
           double score = D_INF;
           if (lane < S.n_dc) {
             int d = lane;
-            const double* pcf = c.pc3(d, jt);
-            const double* tcf = c.lc3(d, jt);
+            kc_f64 pcf = c.pc3(d, jt);
+            kc_f64 tcf = c.lc3(d, jt);
             double best = D_INF;
             for (int n = 1; n <= S.max_gpj; ++n)
               for (int q = 0; q < S.n_freq; ++q) {
@@ -1795,17 +1844,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
       } else {
         d_sel = (int)rbelow(c.rng, (uint32_t)S.n_dc);
       }
-      double lnet = S.wan_lat[ing * S.n_dc + d_sel];
-      double bw = S.wan_bw[ing * S.n_dc + d_sel];
+      d_sel = sub_uniform_i32(d_sel);
+      double lnet = launch_const(S.wan_lat)[ing * S.n_dc + d_sel];
+      double bw = launch_const(S.wan_bw)[ing * S.n_dc + d_sel];
       double xfer = bw > 0.0 ? S.payload_gb[jt] / bw : 0.0;
       // push transfer record
-      int cand = INT_MAX;
-      for (int k = lane; k < S.tcap; k += SUBW) {
-        if (c.l_xt[k] >= D_INF) { cand = k; break; }
-      }
-#pragma unroll
-      for (int off = SUBW / 2; off > 0; off >>= 1)
-        cand = min(cand, __shfl_xor(cand, off, 64));
+      int cand = sub_first_empty(c.l_xt, 0, S.tcap);
       if (cand == INT_MAX) {
         if (lane == 0) atomicOr(&S.err[c.r], ERR_XFER_OVF);
       } else if (lane == 0) {
@@ -1851,8 +1895,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
       // ===== WAN transfer complete: admission =====
       int64_t at = (int64_t)c.r * S.tcap + idx;
       XRec xr = S.x_rec[at];
-      int d = xr.dc;
-      int jt = xr.jtype;
+      int d = sub_uniform_i32(xr.dc);
+      int jt = sub_uniform_i32(xr.jtype);
       double size = xr.size;
       float netlat = xr.netlat;
       int jid = xr.jid;
@@ -1882,10 +1926,10 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
     } else if (kind == 2) {
       // ===== job finish =====
       int slot = idx;
-      int d = S.slot_dc[slot];
+      int d = sub_uniform_i32(c.slot_dc(slot));
       int64_t at = sbase + slot;
-      int jt = S.s_jtype[at];
-      int n = S.s_gpus[at];
+      int jt = sub_uniform_i32(S.s_jtype[at]);
+      int n = sub_uniform_i32(S.s_gpus[at]);
       SRec srv = S.s_rec[at];
       double size = srv.size;
       double fused = srv.fused;
@@ -1983,8 +2027,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
           break;
         }
       } else {
-        drain_queues<ALGO>(c, d, t_min);
-        rescan_dc_min(c, d);
+        // the rescan above left the cache exact and start_job keeps it
+        // exact, except when a started job ties the minimum: then only the
+        // full scan's lane-order tie-break gives the slot.  The 8-lane
+        // build always rescans (it stays the reference for the skip).
+        bool tie = drain_queues<ALGO>(c, d, t_min);
+        if (tie || SUBW != 64) rescan_dc_min(c, d);
       }
 
     } else {
@@ -2256,6 +2304,81 @@ std::vector<torch::Tensor> rl_forward_debug(torch::Tensor pw,
     throw std::runtime_error(std::string("rl_forward_kernel: ") +
                              hipGetErrorString(e));
   return {out_dc, out_g};
+}
+
+// standalone drivers for the subgroup reduction helpers (test/verification
+// path): one wavefront per row runs the production device functions
+__global__ void __launch_bounds__(64)
+wave_reduce_debug_kernel(const double* vals, const int* idx, double* v_lane,
+                         int* o_lane, double* v_idx, int* o_idx) {
+  int64_t row = blockIdx.x;
+  int lane = threadIdx.x;
+  double x = vals[row * 64 + lane];
+  int ix = idx[row * 64 + lane];
+  int wl;
+  double a = wave_argmin_f64(x, wl);
+  double b;
+  int bi;
+  wave_argmin_idx_f64(x, ix, b, bi);
+  if (lane == 0) {
+    v_lane[row] = a;
+    o_lane[row] = wl;
+    v_idx[row] = b;
+    o_idx[row] = bi;
+  }
+}
+
+std::vector<torch::Tensor> wave_reduce_debug(torch::Tensor vals,
+                                             torch::Tensor idx) {
+  TORCH_CHECK(SUBW == 64, "wave_reduce_debug drives the 64-lane reductions");
+  TORCH_CHECK(vals.is_cuda() && idx.is_cuda() &&
+              vals.dtype() == torch::kFloat64 && idx.dtype() == torch::kInt32);
+  TORCH_CHECK(vals.dim() == 2 && vals.size(1) == 64 &&
+              idx.sizes() == vals.sizes());
+  vals = vals.contiguous();
+  idx = idx.contiguous();
+  int64_t B = vals.size(0);
+  auto v_lane = torch::empty({B}, vals.options());
+  auto o_lane = torch::empty({B}, idx.options());
+  auto v_idx = torch::empty({B}, vals.options());
+  auto o_idx = torch::empty({B}, idx.options());
+  if (B == 0) return {v_lane, o_lane, v_idx, o_idx};
+  hipStream_t stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(wave_reduce_debug_kernel, dim3((unsigned)B), dim3(64), 0,
+                     stream, vals.data_ptr<double>(), idx.data_ptr<int>(),
+                     v_lane.data_ptr<double>(), o_lane.data_ptr<int>(),
+                     v_idx.data_ptr<double>(), o_idx.data_ptr<int>());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    throw std::runtime_error(std::string("wave_reduce_debug_kernel: ") +
+                             hipGetErrorString(e));
+  return {v_lane, o_lane, v_idx, o_idx};
+}
+
+__global__ void __launch_bounds__(64)
+first_empty_debug_kernel(const double* rows, int L, int* out) {
+  int64_t row = blockIdx.x;
+  int k = sub_first_empty(rows + row * L, 0, L);
+  if (threadIdx.x == 0) out[row] = k;
+}
+
+torch::Tensor first_empty_debug(torch::Tensor rows) {
+  TORCH_CHECK(rows.is_cuda() && rows.dtype() == torch::kFloat64 &&
+              rows.dim() == 2 && rows.size(1) >= 1 &&
+              rows.size(1) < (1 << 30));
+  rows = rows.contiguous();
+  int64_t B = rows.size(0);
+  auto out = torch::empty({B}, rows.options().dtype(torch::kInt32));
+  if (B == 0) return out;
+  hipStream_t stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(first_empty_debug_kernel, dim3((unsigned)B), dim3(64), 0,
+                     stream, rows.data_ptr<double>(), (int)rows.size(1),
+                     out.data_ptr<int>());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    throw std::runtime_error(std::string("first_empty_debug_kernel: ") +
+                             hipGetErrorString(e));
+  return out;
 }
 
 // ---------------- host side ----------------
@@ -2543,4 +2666,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",
         py::arg("pw"), py::arg("obs"), py::arg("hid"), py::arg("n_dc"),
         py::arg("n_g"));
+  m.def("wave_reduce_debug", &dcg::wave_reduce_debug,
+        "production wave_argmin_f64 / wave_argmin_idx_f64 over each row of "
+        "(vals[B,64] f64, idx[B,64] i32) -> (value, lane, value, index)",
+        py::arg("vals"), py::arg("idx"));
+  m.def("first_empty_debug", &dcg::first_empty_debug,
+        "production first-empty-slot search over each row of rows[B,L] f64 "
+        "-> lowest k with rows[k] >= 1e300, INT_MAX if none",
+        py::arg("rows"));
 }
