@@ -497,10 +497,6 @@ class BatchedEngine:
             # island via a CU-masked stream: the advance never dispatches
             # there, and the train stream's kernels land immediately.
             try:
-                # resident-grid cap only when the update-rate controller is
-                # active (it shortens the serial catch-up); throughput mode
-                # prefers the full grid (~20% more events/s, measured)
-                self._sim.set_resident_cap(self._rl_target_ups > 0)
                 self._sim.enable_masked_stream(self._reserve_cus)
             except RuntimeError as e:
                 # masked stream unavailable: overlap still works, slower

@@ -221,7 +221,9 @@ struct EngineDesc {
   int* pend_ing;                  // [r]
   int* pend_jt;                   // [r]
   int* pend_dc;                   // [r] (drain: source DC)
-  int* pend_from_inf;             // [r] (drain: which queue the job came from)
+  int* pend_from_inf;             // [r] (drain: 1 = popped from the inference
+                                  //   queue; kept for the host-side state
+                                  //   layout — the resume reads pend_jt)
   double* pend_enq;               // [r] (drain: the popped job's enqueue time)
   // per-job RL obs traces (the action/mask bytes live in SRec/XRec;
   // arrival path keeps nrew = g_idx+1 unclamped, drain path clamped —
@@ -319,6 +321,30 @@ struct Hot {
   int q_head[MAX_DC * 2];
 };
 
+constexpr int RL_MAX_HID = 256;
+constexpr int RL_MAX_OBS = 64;
+constexpr int RL_MAX_LOG = 16;
+// actor-forward LDS scratch: obs, two activation buffers, head logits
+constexpr size_t RL_LDS_BYTES =
+    (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float);
+
+// Byte sizes of the parts of one replica's dynamic-LDS slice, in carve
+// order: Hot, then (SUBW==64 only — at 8 replicas per wave they would exceed
+// the LDS budget) the s_finish and x_time mirrors, then (chsac only) the
+// actor-forward scratch.  The kernel carves by it, advance() sizes the
+// launch by it.
+struct LdsSizes {
+  size_t hot, fin, xt, rl;
+  __host__ __device__ size_t stride() const { return hot + fin + xt + rl; }
+};
+__host__ __device__ inline LdsSizes lds_sizes(int total_slots, int tcap,
+                                              bool chsac) {
+  return {(sizeof(Hot) + 15) & ~size_t(15),
+          SUBW == 64 ? (size_t)total_slots * sizeof(double) : 0,
+          SUBW == 64 ? (size_t)tcap * sizeof(double) : 0,
+          chsac ? RL_LDS_BYTES : 0};
+}
+
 // ---------------- replica context ----------------
 struct Ctx {
   const EngineDesc* S;
@@ -379,6 +405,14 @@ struct Ctx {
     int h = static_cast<int>(fmod(t, 86400.0) / 3600.0);
     return S->price24[h];
   }
+};
+
+// RL trace a chsac arrival carries into its WAN transfer; a null pointer
+// stands for a plain (untraced) arrival
+struct JobTrace {
+  const float* s0;          // observation at decision time [obs_dim]
+  int adc, ag, mdc, mg;     // action and mask bytes
+  int n_rew;                // the RL-chosen n (unclamped g+1)
 };
 
 // recompute a DC's cached min finish (wave-cooperative)
@@ -481,9 +515,9 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
   int free = c.free_gpus(d);
   if (ALGO == A_JOINT_NF) {
     GridPick g = S.fp32_score
-        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+        ? wave_grid_argmin<float>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                S.n_freq, S.max_gpj, 0, 0.0, 0.0, false, 0.0)
-        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+        : wave_grid_argmin<double>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                            S.n_freq, S.max_gpj, 0, 0.0, 0.0, false, 0.0);
     n_out = g.n; f_out = g.f;
   } else if (ALGO == A_BANDIT) {
@@ -510,18 +544,18 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
     int obj = price > 0.0 ? 2 : 1;
     double ci = price > 0.0 ? 0.0 : S.carbon[d];
     GridPick g = S.fp32_score
-        ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+        ? wave_grid_argmin<float>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                S.n_freq, S.max_gpj, obj, ci, price, false, 0.0)
-        : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+        : wave_grid_argmin<double>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                            S.n_freq, S.max_gpj, obj, ci, price, false, 0.0);
     n_out = g.n; f_out = g.f;
   } else if (ALGO == A_DEBUG) {
     n_out = S.num_fixed;
     f_out = S.fixed_freq > 0 ? S.fixed_freq
             : (S.fp32_score
-               ? wave_energy_freq_f32(c.pc3(d, jt), c.lc3(d, jt),
+               ? wave_energy_freq<float>(c.pc3(d, jt), c.lc3(d, jt),
                                       c.freq_levels(), S.n_freq, S.num_fixed)
-               : wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+               : wave_energy_freq<double>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                   S.n_freq, S.num_fixed));
   } else {  // heuristic family
     n_out = heuristic_alloc(c, d, jt);
@@ -531,8 +565,10 @@ __device__ void decide_nf(Ctx& c, int d, int jt, float size, double now,
 
 // queue ops (wave-uniform; lane-0 writes).  `enq` is the job's enqueue time
 // at this DC — carried per entry so pops can credit the queueing delay.
+// `front` inserts ahead of the head (a popped job going back) instead of at
+// the tail.
 __device__ bool queue_push(Ctx& c, int d, int jt, double size, float netlat,
-                           int jid, int ing, double enq) {
+                           int jid, int ing, double enq, bool front = false) {
   const EngineDesc& S = *c.S;
   int ql = d * 2 + jt;
   int len = c.hs->q_len[ql];
@@ -540,7 +576,8 @@ __device__ bool queue_push(Ctx& c, int d, int jt, double size, float netlat,
     if (c.lane == 0) atomicOr(&S.err[c.r], ERR_QUEUE_OVF);
     return false;
   }
-  int pos = (c.hs->q_head[ql] + len) % S.qcap;
+  int pos = front ? (c.hs->q_head[ql] - 1 + S.qcap) % S.qcap
+                  : (c.hs->q_head[ql] + len) % S.qcap;
   if (c.lane == 0) {
     int64_t at = ((int64_t)(c.r * S.n_dc + d) * 2 + jt) * S.qcap + pos;
     S.q_pay[at * 2] = size;
@@ -551,33 +588,7 @@ __device__ bool queue_push(Ctx& c, int d, int jt, double size, float netlat,
       S.q_jid[aux] = jid;
       S.q_ing[aux] = (char)ing;
     }
-    c.hs->q_len[ql] = len + 1;
-  }
-  store_fence();
-  return true;
-}
-
-__device__ bool queue_push_front(Ctx& c, int d, int jt, double size,
-                                 float netlat, int jid, int ing, double enq) {
-  const EngineDesc& S = *c.S;
-  int ql = d * 2 + jt;
-  int len = c.hs->q_len[ql];
-  if (len >= S.qcap) {
-    if (c.lane == 0) atomicOr(&S.err[c.r], ERR_QUEUE_OVF);
-    return false;
-  }
-  int pos = (c.hs->q_head[ql] - 1 + S.qcap) % S.qcap;
-  if (c.lane == 0) {
-    int64_t at = ((int64_t)(c.r * S.n_dc + d) * 2 + jt) * S.qcap + pos;
-    S.q_pay[at * 2] = size;
-    S.q_pay[at * 2 + 1] = enq;
-    if (c.r == S.log_replica) {
-      int64_t aux = ((int64_t)ql) * S.qcap + pos;
-      S.q_netlat[aux] = netlat;
-      S.q_jid[aux] = jid;
-      S.q_ing[aux] = (char)ing;
-    }
-    c.hs->q_head[ql] = pos;
+    if (front) c.hs->q_head[ql] = pos;
     c.hs->q_len[ql] = len + 1;
   }
   store_fence();
@@ -610,6 +621,19 @@ __device__ bool queue_pop(Ctx& c, int d, int jt, double& size, float& netlat,
   return true;
 }
 
+// pop the job a drain of DC d serves next: the inference queue first when
+// inf_priority, else (or when that is empty) the training queue (the chsac
+// one-job drain; drain_queues keeps the same three lines inline)
+__device__ bool queue_pop_next(Ctx& c, int d, int& jt, double& size,
+                               float& netlat, int& jid, int& ing,
+                               double& enq) {
+  if (c.S->inf_priority && queue_pop(c, d, 0, size, netlat, jid, ing, enq))
+    jt = 0;
+  else if (queue_pop(c, d, 1, size, netlat, jid, ing, enq)) jt = 1;
+  else return false;
+  return true;
+}
+
 // drain queues after a completion (inference first; reference :839-927);
 // returns true if any started job tied the DC's cached min finish (see
 // start_job) so the caller must rescan
@@ -622,6 +646,8 @@ __device__ bool drain_queues(Ctx& c, int d, double now) {
     float netlat;
     int jid, ing;
     int jt;
+    // queue_pop_next, written out: every call form of it measured here
+    // changed this hot loop's code generation (profiles/README.md)
     if (S.inf_priority && queue_pop(c, d, 0, size, netlat, jid, ing, enq)) jt = 0;
     else if (queue_pop(c, d, 1, size, netlat, jid, ing, enq)) jt = 1;
     else break;
@@ -631,10 +657,10 @@ __device__ bool drain_queues(Ctx& c, int d, double now) {
       // carbon_cost (simulator_paper_multi.py:909-920), unlike its admission
       // path which prefers cost when a price is set (:622-645)
       GridPick g = S.fp32_score
-          ? wave_grid_argmin_f32(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+          ? wave_grid_argmin<float>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                                  S.n_freq, S.max_gpj, 1, S.carbon[d], 0.0,
                                  false, 0.0)
-          : wave_grid_argmin(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+          : wave_grid_argmin<double>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
                              S.n_freq, S.max_gpj, 1, S.carbon[d], 0.0,
                              false, 0.0);
       n = g.n; f = g.f;
@@ -651,6 +677,70 @@ __device__ bool drain_queues(Ctx& c, int d, double now) {
     if (c.lane == 0) c.hs->sum_wait += fmax(0.0, now - enq);
   }
   return tie;
+}
+
+// inter-arrival time of the jtype-jt process after an arrival at time t:
+// Poisson, or faithful non-accumulating sinusoid thinning (reference
+// arrivals.py:35-48); D_INF when the process is off
+__device__ double draw_interarrival(Ctx& c, int jt, double t) {
+  const EngineDesc& S = *c.S;
+  double rate = S.arr_rate[jt];
+  int mode = S.arr_mode[jt];
+  double amp = S.arr_amp[jt];
+  double period = S.arr_period[jt];
+  double ia = D_INF;
+  if (mode == 0 && rate > 0) {
+    ia = rexp(c.rng, rate);
+  } else if (mode == 1) {
+    double max_rate = rate * (1.0 + fabs(amp));
+    if (max_rate > 0) {
+      for (int it = 0; it < 4096; ++it) {
+        double w = rexp(c.rng, max_rate);
+        double lam = fmax(0.0, rate * (1.0 + amp *
+            sin(2.0 * M_PI * fmod(t + w, period) / period)));
+        if (u01(c.rng) <= lam / max_rate) { ia = w; break; }
+      }
+    }
+  }
+  return ia;
+}
+
+// push the WAN transfer of an arrival routed to DC d_sel into the first empty
+// transfer slot; `tr` (chsac) rides along as the RL part of the record
+// (reference :570-588), n_rew being the RL-chosen n
+__device__ void push_transfer(Ctx& c, double now, int jt, int ing, double size,
+                              int jid, int d_sel,
+                              const JobTrace* tr = nullptr) {
+  const EngineDesc& S = *c.S;
+  double lnet = launch_const(S.wan_lat)[ing * S.n_dc + d_sel];
+  double bw = launch_const(S.wan_bw)[ing * S.n_dc + d_sel];
+  double xfer = bw > 0.0 ? S.payload_gb[jt] / bw : 0.0;
+  int cand = sub_first_empty(c.l_xt, 0, S.tcap);
+  if (tr && cand != INT_MAX)  // the s0 trace (lane-parallel over obs_dim)
+    for (int k = c.lane; k < S.obs_dim; k += SUBW)
+      S.x_s0[((int64_t)c.r * S.tcap + cand) * S.obs_dim + k] = tr->s0[k];
+  if (cand == INT_MAX) {
+    if (c.lane == 0) atomicOr(&S.err[c.r], ERR_XFER_OVF);
+  } else if (c.lane == 0) {
+    int64_t at = (int64_t)c.r * S.tcap + cand;
+    c.l_xt[cand] = now + lnet + xfer;
+    XRec* xr = &S.x_rec[at];
+    xr->size = size;
+    xr->netlat = (float)lnet;
+    xr->jid = jid;
+    xr->dc = (unsigned char)d_sel;
+    xr->jtype = (unsigned char)jt;
+    xr->ing = (unsigned char)ing;
+    if (tr) {
+      xr->nsel = (short)tr->n_rew;
+      xr->adc = (unsigned char)tr->adc;
+      xr->ag = (unsigned char)tr->ag;
+      xr->mdc = (unsigned char)tr->mdc;
+      xr->mg = (unsigned char)tr->mg;
+    }
+    xr->has_rl = tr != nullptr;
+  }
+  store_fence();
 }
 
 // accrue energy + util across DCs to time t (lanes 0..n_dc-1)
@@ -1027,8 +1117,8 @@ __device__ int rl_min_n_for_sla(Ctx& c, int d, int jt, double size, double f) {
 // reference jobs never carry deadlines — Job.deadline is always None)
 __device__ double rl_energy_freq(Ctx& c, int d, int jt, int n) {
   const EngineDesc& S = *c.S;
-  return wave_energy_freq(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
-                          S.n_freq, n);
+  return wave_energy_freq<double>(c.pc3(d, jt), c.lc3(d, jt), c.freq_levels(),
+                                  S.n_freq, n);
 }
 
 // ---------------- device-side actor forward + sampling ----------------
@@ -1037,9 +1127,6 @@ __device__ double rl_energy_freq(Ctx& c, int d, int jt, int n) {
 // (hid->hid->n_dc / n_g).  Weights are [in][out]-major, so at every input
 // index the SUBW lanes read consecutive floats (fully coalesced, L2-resident
 // at ~1.1 MB total); activations live in LDS.  ~280k FMA per call.
-constexpr int RL_MAX_HID = 256;
-constexpr int RL_MAX_OBS = 64;
-constexpr int RL_MAX_LOG = 16;
 
 __device__ void rl_dense(const float* x, int in, const float* Wt,
                          const float* b, int out, float* y, int lane,
@@ -1126,8 +1213,11 @@ __device__ void rl_serve_inline(Ctx& c, double now, int& a_dc, int& a_g,
   a_g = rl_pick(c, c.l_logits + 8, mg, S.n_g);
 }
 
-// start a job carrying an RL trace; returns chosen slot via start_job's path.
-// (duplicates start_job, then fills the rl trace of the slot just used)
+// start a job carrying an RL trace (chsac).  Deliberately NOT folded into
+// start_job: with the trace as an optional argument of one start_job the
+// non-CHSAC kernels stayed identical, but the RL loop measured ~3% slower
+// (profiles/README.md), so any change to slot allocation, SRec layout or the
+// min-finish cache still has to be made in both.
 __device__ void rl_start_job(Ctx& c, int d, int jt, double size, float netlat,
                              int jid, int ing, int n, double f, double now,
                              const float* s0, int a_dc, int a_g,
@@ -1295,29 +1385,6 @@ __device__ __attribute__((noinline)) int rl_elastic_preempt_all(
   return count;
 }
 
-// chsac drains AT MOST ONE queued job per finish via a fresh policy action
-// (reference :849-890); returns true if a request was issued (pause)
-__device__ bool rl_try_drain_request(Ctx& c, int d, double now) {
-  const EngineDesc& S = *c.S;
-  double qsize, qenq;
-  float qnetlat;
-  int qjid, qing;
-  bool popped = false;
-  int from_inf = 0;
-  if (c.free_gpus(d) > 0) {
-    if (S.inf_priority && queue_pop(c, d, 0, qsize, qnetlat, qjid, qing, qenq)) {
-      popped = true;
-      from_inf = 1;
-    } else if (queue_pop(c, d, 1, qsize, qnetlat, qjid, qing, qenq)) {
-      popped = true;
-    }
-  }
-  if (popped)
-    rl_request(c, PEND_DRAIN, now, from_inf ? 0 : 1, qing, qsize, qnetlat,
-               qjid, d, from_inf, qenq);
-  return popped;
-}
-
 // request the RL action for the pool entry at the cursor
 __device__ void rl_request_realloc(Ctx& c, double now) {
   const EngineDesc& S = *c.S;
@@ -1328,58 +1395,20 @@ __device__ void rl_request_realloc(Ctx& c, double now) {
 }
 
 // ---- action EXECUTION bodies, shared by the host resume path and the
-// in-kernel serving path ----
-
-// complete an RL-routed arrival: push the WAN transfer carrying the trace
-// (reference :570-588 with the stashed action)
-__device__ void rl_do_arrival(Ctx& c, double now, int jt, int ing,
-                              double size, int jid, int a_dc, int a_g,
-                              const float* s0, int mdc, int mg) {
-  const EngineDesc& S = *c.S;
-  int d_sel = a_dc;
-  int n_sel = a_g + 1;
-  double lnet = S.wan_lat[ing * S.n_dc + d_sel];
-  double bw = S.wan_bw[ing * S.n_dc + d_sel];
-  double xfer = bw > 0.0 ? S.payload_gb[jt] / bw : 0.0;
-  int cand = sub_first_empty(c.l_xt, 0, S.tcap);
-  if (cand == INT_MAX) {
-    if (c.lane == 0) atomicOr(&S.err[c.r], ERR_XFER_OVF);
-    return;
-  }
-  int64_t at = (int64_t)c.r * S.tcap + cand;
-  for (int k = c.lane; k < S.obs_dim; k += SUBW)
-    S.x_s0[at * S.obs_dim + k] = s0[k];
-  if (c.lane == 0) {
-    c.l_xt[cand] = now + lnet + xfer;
-    XRec* xr = &S.x_rec[at];
-    xr->size = size;
-    xr->netlat = (float)lnet;
-    xr->jid = jid;
-    xr->dc = (unsigned char)d_sel;
-    xr->jtype = (unsigned char)jt;
-    xr->ing = (unsigned char)ing;
-    xr->nsel = (short)n_sel;
-    xr->adc = (unsigned char)a_dc;
-    xr->ag = (unsigned char)a_g;
-    xr->mdc = (unsigned char)mdc;
-    xr->mg = (unsigned char)mg;
-    xr->has_rl = 1;
-  }
-  store_fence();
-}
+// in-kernel serving path (an RL-routed arrival is push_transfer with the
+// trace) ----
 
 // execute a drain action on the popped job: start on the RL's target DC, or
 // push back at the FRONT of the source queue when the target has no free
 // GPUs (reference :849-890)
-__device__ void rl_do_drain_action(Ctx& c, double now, int src_d,
-                                   int from_inf, int jt, int ing, double size,
-                                   float netlat, int jid, double enq,
-                                   int a_dc, int a_g, const float* s0,
-                                   int mdc, int mg) {
+__device__ void rl_do_drain_action(Ctx& c, double now, int src_d, int jt,
+                                   int ing, double size, float netlat,
+                                   int jid, double enq, int a_dc, int a_g,
+                                   const float* s0, int mdc, int mg) {
   const EngineDesc& S = *c.S;
   int d_tgt = a_dc;
   if (c.free_gpus(d_tgt) <= 0) {
-    queue_push_front(c, src_d, from_inf ? 0 : 1, size, netlat, jid, ing, enq);
+    queue_push(c, src_d, jt, size, netlat, jid, ing, enq, /*front=*/true);
   } else {
     int n_sel = max(1, min(min(a_g + 1, c.free_gpus(d_tgt)), S.max_gpj));
     double f = rl_energy_freq(c, d_tgt, jt, n_sel);
@@ -1389,33 +1418,58 @@ __device__ void rl_do_drain_action(Ctx& c, double now, int src_d,
   }
 }
 
-// in-kernel one-job queue drain (serve_device): pop, serve, execute — the
-// replica continues its event loop with no host round-trip
-__device__ void rl_drain_inline(Ctx& c, int d, double now) {
+// chsac drains AT MOST ONE queued job per finish via a fresh policy action
+// (reference :849-890).  Host serving (`serve` false) requests the action and
+// returns true (the replica pauses); device serving serves and executes it in
+// place, so the replica continues its event loop with no host round-trip.
+__device__ bool rl_drain_one(Ctx& c, int d, double now, bool serve) {
   const EngineDesc& S = *c.S;
-  double qsize, qenq;
-  float qnetlat;
-  int qjid, qing;
-  int from_inf = 0;
-  bool popped = false;
-  if (c.free_gpus(d) > 0) {
-    if (S.inf_priority && queue_pop(c, d, 0, qsize, qnetlat, qjid, qing, qenq)) {
-      popped = true;
-      from_inf = 1;
-    } else if (queue_pop(c, d, 1, qsize, qnetlat, qjid, qing, qenq)) {
-      popped = true;
-    }
+  double size, enq;
+  float netlat;
+  int jid, ing, jt;
+  if (c.free_gpus(d) <= 0 ||
+      !queue_pop_next(c, d, jt, size, netlat, jid, ing, enq))
+    return false;
+  if (!serve) {
+    rl_request(c, PEND_DRAIN, now, jt, ing, size, netlat, jid, d, jt == 0,
+               enq);
+    return true;
   }
-  if (!popped) return;
   int a_dc, a_g, mdc, mg;
   rl_serve_inline(c, now, a_dc, a_g, mdc, mg);
-  rl_do_drain_action(c, now, d, from_inf, from_inf ? 0 : 1, qing, qsize,
-                     qnetlat, qjid, qenq, a_dc, a_g, c.l_obs, mdc, mg);
+  rl_do_drain_action(c, now, d, jt, ing, size, netlat, jid, enq, a_dc, a_g,
+                     c.l_obs, mdc, mg);
+  return false;
+}
+
+// one step of the elastic reallocation chain (reference
+// _rl_reallocate_training_jobs :498-534): pool entry `cur` goes back on its
+// DC — re-queued on the training queue when that has no free GPUs (oracle's
+// fix of reference Appendix A.6 job-stranding), else resumed at the fresh
+// action's n (clamped) and its energy-optimal f, keeping the trace it was
+// preempted with.  Returns the entry's DC.
+__device__ int rl_realloc_entry(Ctx& c, int cur, int a_g, int mdc, int mg,
+                                double now) {
+  const EngineDesc& S = *c.S;
+  int64_t pb = (int64_t)c.r * S.pp_cap + cur;
+  int d_src = S.pp_dc[pb];
+  if (c.free_gpus(d_src) <= 0) {
+    queue_push(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
+               S.pp_jid[pb], S.pp_ing[pb], now);
+  } else {
+    int n_rl = max(1, min(min(a_g + 1, c.free_gpus(d_src)), S.max_gpj));
+    double f = rl_energy_freq(c, d_src, 1, n_rl);
+    rl_start_job(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
+                 S.pp_jid[pb], S.pp_ing[pb], n_rl, f, now,
+                 &S.pp_s0[pb * S.obs_dim], S.pp_adc[pb], S.pp_ag[pb],
+                 mdc, mg, S.pp_nrew[pb], S.pp_done[pb], S.pp_pcount[pb],
+                 S.pp_has_rl[pb], S.pp_start[pb]);
+  }
+  return d_src;
 }
 
 // in-kernel elastic reallocation chain (serve_device): fresh obs + actor
-// forward per pool entry, all within this launch (reference
-// _rl_reallocate_training_jobs :498-534; failed resumes re-queue)
+// forward per pool entry, all within this launch
 __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
                                                             double now) {
   const EngineDesc& S = *c.S;
@@ -1423,20 +1477,7 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
   for (int cur = 0; cur < cnt; ++cur) {
     int a_dc, a_g, mdc, mg;
     rl_serve_inline(c, now, a_dc, a_g, mdc, mg);
-    int64_t pb = (int64_t)c.r * S.pp_cap + cur;
-    int d_src = S.pp_dc[pb];
-    if (c.free_gpus(d_src) <= 0) {
-      queue_push(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
-                 S.pp_jid[pb], S.pp_ing[pb], now);
-    } else {
-      int n_rl = max(1, min(min(a_g + 1, c.free_gpus(d_src)), S.max_gpj));
-      double f = rl_energy_freq(c, d_src, 1, n_rl);
-      rl_start_job(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
-                   S.pp_jid[pb], S.pp_ing[pb], n_rl, f, now,
-                   &S.pp_s0[pb * S.obs_dim], S.pp_adc[pb], S.pp_ag[pb],
-                   mdc, mg, S.pp_nrew[pb], S.pp_done[pb], S.pp_pcount[pb],
-                   S.pp_has_rl[pb], S.pp_start[pb]);
-    }
+    rl_realloc_entry(c, cur, a_g, mdc, mg, now);
   }
   if (c.lane == 0) {
     S.pp_count[c.r] = 0;
@@ -1483,29 +1524,22 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
   bool paused = false;
   bool skip_loop = false;  // realloc chain pending: bypass the event loop
 
-  // ---- carve the dynamic-LDS region ----
-  // SUBW==64: per replica, Hot + s_finish mirror + x_time mirror.
-  // SUBW==8: Hot only (the mirrors would exceed the LDS budget at 8
-  // replicas/wave); l_fin/l_xt then alias the replica's global rows.
+  // ---- carve the dynamic-LDS region (lds_sizes) ----
+  // SUBW==8 has no mirrors: l_fin/l_xt alias the replica's global rows.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   {
-    size_t hot_sz = (sizeof(Hot) + 15) & ~size_t(15);
-    size_t fin_sz = SUBW == 64 ? (size_t)S.total_slots * sizeof(double) : 0;
-    size_t xt_sz = SUBW == 64 ? (size_t)S.tcap * sizeof(double) : 0;
-    size_t rl_sz = ALGO == A_CHSAC
-        ? (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float) : 0;
-    size_t stride = hot_sz + fin_sz + xt_sz + rl_sz;
-    char* base = smem + (threadIdx.x / SUBW) * stride;
+    const LdsSizes z = lds_sizes(S.total_slots, S.tcap, ALGO == A_CHSAC);
+    char* base = smem + (threadIdx.x / SUBW) * z.stride();
     c.hs = reinterpret_cast<Hot*>(base);
     if (SUBW == 64) {
-      c.l_fin = reinterpret_cast<double*>(base + hot_sz);
-      c.l_xt = reinterpret_cast<double*>(base + hot_sz + fin_sz);
+      c.l_fin = reinterpret_cast<double*>(base + z.hot);
+      c.l_xt = reinterpret_cast<double*>(base + z.hot + z.fin);
     } else {
       c.l_fin = S.s_finish + sbase;
       c.l_xt = S.x_time + (int64_t)c.r * S.tcap;
     }
     if (ALGO == A_CHSAC) {
-      float* rb = reinterpret_cast<float*>(base + hot_sz + fin_sz + xt_sz);
+      float* rb = reinterpret_cast<float*>(base + z.hot + z.fin + z.xt);
       c.l_obs = rb;
       c.l_act_a = rb + RL_MAX_OBS;
       c.l_act_b = c.l_act_a + RL_MAX_HID;
@@ -1569,30 +1603,15 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
     int jid = S.pend_jid[c.r];
     if (pk == PEND_ARRIVAL) {
       // complete the arrival: RL chose (dc, g); push the WAN transfer
-      rl_do_arrival(c, c.now, jt, ing, size, jid, a_dc, a_g, s0, mdc, mg);
+      JobTrace tr{s0, a_dc, a_g, mdc, mg, a_g + 1};
+      push_transfer(c, c.now, jt, ing, size, jid, a_dc, &tr);
     } else if (pk == PEND_DRAIN) {
-      // one queued job, RL chose a target DC + g
-      rl_do_drain_action(c, c.now, S.pend_dc[c.r], S.pend_from_inf[c.r], jt,
-                         ing, size, netlat, jid, S.pend_enq[c.r],
-                         a_dc, a_g, s0, mdc, mg);
+      // one queued job (pend_jt names its queue), RL chose a target DC + g
+      rl_do_drain_action(c, c.now, S.pend_dc[c.r], jt, ing, size, netlat, jid,
+                         S.pend_enq[c.r], a_dc, a_g, s0, mdc, mg);
     } else {  // PEND_REALLOC: resume the pool entry at the cursor on its DC
       int cur = S.pp_cursor[c.r];
-      int64_t pb = (int64_t)c.r * S.pp_cap + cur;
-      int d_src = S.pp_dc[pb];
-      if (c.free_gpus(d_src) <= 0) {
-        // no free GPUs: re-queue on the training queue (oracle's fix of
-        // reference Appendix A.6 job-stranding)
-        queue_push(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
-                   S.pp_jid[pb], S.pp_ing[pb], c.now);
-      } else {
-        int n_rl = max(1, min(min(a_g + 1, c.free_gpus(d_src)), S.max_gpj));
-        double f = rl_energy_freq(c, d_src, 1, n_rl);
-        rl_start_job(c, d_src, 1, S.pp_size[pb], S.pp_netlat[pb],
-                     S.pp_jid[pb], S.pp_ing[pb], n_rl, f, c.now,
-                     &S.pp_s0[pb * S.obs_dim], S.pp_adc[pb], S.pp_ag[pb],
-                     mdc, mg, S.pp_nrew[pb], S.pp_done[pb], S.pp_pcount[pb],
-                     S.pp_has_rl[pb], S.pp_start[pb]);
-      }
+      int d_src = rl_realloc_entry(c, cur, a_g, mdc, mg, c.now);
       int nxt = cur + 1;
       if (nxt < S.pp_count[c.r]) {
         if (lane == 0) S.pp_cursor[c.r] = nxt;
@@ -1610,7 +1629,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
         }
         store_fence();
         // reallocation finished -> the deferred one-job queue drain
-        if (rl_try_drain_request(c, d_src, c.now)) {
+        // (a paused request exists only under host serving)
+        if (rl_drain_one(c, d_src, c.now, false)) {
           skip_loop = true;
           paused = true;
         }
@@ -1743,33 +1763,15 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
         // schedule the next arrival first (RNG order differs from the scalar
         // engines; distributionally identical), then pause for the policy
         double ia_rl = D_INF;
-        if (!S.trace_mode) {
-          double rate = S.arr_rate[jt];
-          int mode = S.arr_mode[jt];
-          double amp = S.arr_amp[jt];
-          double period = S.arr_period[jt];
-          if (mode == 0 && rate > 0) {
-            ia_rl = rexp(c.rng, rate);
-          } else if (mode == 1) {
-            double max_rate = rate * (1.0 + fabs(amp));
-            if (max_rate > 0) {
-              for (int it = 0; it < 4096; ++it) {
-                double w = rexp(c.rng, max_rate);
-                double lam = fmax(0.0, rate * (1.0 + amp *
-                    sin(2.0 * M_PI * fmod(t_min + w, period) / period)));
-                if (u01(c.rng) <= lam / max_rate) { ia_rl = w; break; }
-              }
-            }
-          }
-        }
+        if (!S.trace_mode) ia_rl = draw_interarrival(c, jt, t_min);
         if (lane == 0 && !S.trace_mode) c.hs->arr_next[idx] = t_min + ia_rl;
         lds_fence();
         if (S.serve_device) {
           // in-kernel policy: forward + sample + execute, no pause
           int a_dc, a_g, mdc, mg;
           rl_serve_inline(c, t_min, a_dc, a_g, mdc, mg);
-          rl_do_arrival(c, t_min, jt, ing, size, jid, a_dc, a_g, c.l_obs,
-                        mdc, mg);
+          JobTrace tr{c.l_obs, a_dc, a_g, mdc, mg, a_g + 1};
+          push_transfer(c, t_min, jt, ing, size, jid, a_dc, &tr);
         } else {
           rl_request(c, PEND_ARRIVAL, t_min, jt, ing, size, 0.0f, jid,
                      -1, 0, t_min);
@@ -1845,48 +1847,10 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
         d_sel = (int)rbelow(c.rng, (uint32_t)S.n_dc);
       }
       d_sel = sub_uniform_i32(d_sel);
-      double lnet = launch_const(S.wan_lat)[ing * S.n_dc + d_sel];
-      double bw = launch_const(S.wan_bw)[ing * S.n_dc + d_sel];
-      double xfer = bw > 0.0 ? S.payload_gb[jt] / bw : 0.0;
-      // push transfer record
-      int cand = sub_first_empty(c.l_xt, 0, S.tcap);
-      if (cand == INT_MAX) {
-        if (lane == 0) atomicOr(&S.err[c.r], ERR_XFER_OVF);
-      } else if (lane == 0) {
-        int64_t at = (int64_t)c.r * S.tcap + cand;
-        c.l_xt[cand] = t_min + lnet + xfer;
-        XRec* xr = &S.x_rec[at];
-        xr->size = size;
-        xr->netlat = (float)lnet;
-        xr->jid = jid;
-        xr->dc = (unsigned char)d_sel;
-        xr->jtype = (unsigned char)jt;
-        xr->ing = (unsigned char)ing;
-        xr->has_rl = 0;
-      }
-      store_fence();
-      // next arrival for this stream (faithful non-accumulating thinning;
-      // reference arrivals.py:35-48); in replay mode it was already set
+      push_transfer(c, t_min, jt, ing, size, jid, d_sel);
+      // next arrival for this stream; in replay mode it was already set
       double ia = D_INF;
-      if (!S.trace_mode) {
-        double rate = S.arr_rate[jt];
-        int mode = S.arr_mode[jt];
-        double amp = S.arr_amp[jt];
-        double period = S.arr_period[jt];
-        if (mode == 0 && rate > 0) {
-          ia = rexp(c.rng, rate);
-        } else if (mode == 1) {
-          double max_rate = rate * (1.0 + fabs(amp));
-          if (max_rate > 0) {
-            for (int it = 0; it < 4096; ++it) {
-              double w = rexp(c.rng, max_rate);
-              double lam = fmax(0.0, rate * (1.0 + amp *
-                  sin(2.0 * M_PI * fmod(t_min + w, period) / period)));
-              if (u01(c.rng) <= lam / max_rate) { ia = w; break; }
-            }
-          }
-        }
-      }
+      if (!S.trace_mode) ia = draw_interarrival(c, jt, t_min);
       if (lane == 0 && !S.trace_mode) c.hs->arr_next[idx] = t_min + ia;
       lds_fence();
       }  // end non-chsac arrival path
@@ -2020,9 +1984,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
             }
           }
         }
-        if (S.serve_device) {
-          rl_drain_inline(c, d, t_min);
-        } else if (rl_try_drain_request(c, d, t_min)) {
+        if (rl_drain_one(c, d, t_min, S.serve_device)) {
           paused = true;
           break;
         }
@@ -2233,6 +2195,13 @@ rl_forward_mfma_kernel(const float* pw, const float* obs, int B, int obs_dim,
   }
 }
 
+// throw if the kernel launch just issued failed
+static void check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
 std::vector<torch::Tensor> rl_forward_mfma(torch::Tensor pw,
                                            torch::Tensor obs,
                                            int64_t hid, int64_t n_dc,
@@ -2249,10 +2218,7 @@ std::vector<torch::Tensor> rl_forward_mfma(torch::Tensor pw,
                      stream, pw.data_ptr<float>(), obs.data_ptr<float>(), B,
                      D, (int)hid, (int)n_dc, (int)n_g,
                      out_dc.data_ptr<float>(), out_g.data_ptr<float>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("rl_forward_mfma_kernel: ") +
-                             hipGetErrorString(e));
+  check_launch("rl_forward_mfma_kernel");
   return {out_dc, out_g};
 }
 
@@ -2264,8 +2230,8 @@ rl_forward_kernel(const float* pw, const float* obs, int B, int obs_dim,
   int slot = (blockIdx.x * blockDim.x + threadIdx.x) / SUBW;
   int lane = threadIdx.x & (SUBW - 1);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  size_t per = (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float);
-  float* rb = reinterpret_cast<float*>(smem + (threadIdx.x / SUBW) * per);
+  float* rb =
+      reinterpret_cast<float*>(smem + (threadIdx.x / SUBW) * RL_LDS_BYTES);
   if (slot >= B) return;
   float* l_obs = rb;
   float* A = rb + RL_MAX_OBS;
@@ -2291,18 +2257,14 @@ std::vector<torch::Tensor> rl_forward_debug(torch::Tensor pw,
   auto out_g = torch::empty({B, n_g}, obs.options());
   int rpb = REPLICAS_PER_BLOCK;
   int blocks = (B + rpb - 1) / rpb;
-  size_t shmem = (size_t)rpb *
-      (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float);
+  size_t shmem = (size_t)rpb * RL_LDS_BYTES;
   hipStream_t stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(rl_forward_kernel, dim3(blocks), dim3(THREADS_PER_BLOCK),
                      shmem, stream, pw.data_ptr<float>(),
                      obs.data_ptr<float>(), B, D, (int)hid, (int)n_dc,
                      (int)n_g, out_dc.data_ptr<float>(),
                      out_g.data_ptr<float>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("rl_forward_kernel: ") +
-                             hipGetErrorString(e));
+  check_launch("rl_forward_kernel");
   return {out_dc, out_g};
 }
 
@@ -2348,10 +2310,7 @@ std::vector<torch::Tensor> wave_reduce_debug(torch::Tensor vals,
                      stream, vals.data_ptr<double>(), idx.data_ptr<int>(),
                      v_lane.data_ptr<double>(), o_lane.data_ptr<int>(),
                      v_idx.data_ptr<double>(), o_idx.data_ptr<int>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("wave_reduce_debug_kernel: ") +
-                             hipGetErrorString(e));
+  check_launch("wave_reduce_debug_kernel");
   return {v_lane, o_lane, v_idx, o_idx};
 }
 
@@ -2374,16 +2333,17 @@ torch::Tensor first_empty_debug(torch::Tensor rows) {
   hipLaunchKernelGGL(first_empty_debug_kernel, dim3((unsigned)B), dim3(64), 0,
                      stream, rows.data_ptr<double>(), (int)rows.size(1),
                      out.data_ptr<int>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("first_empty_debug_kernel: ") +
-                             hipGetErrorString(e));
+  check_launch("first_empty_debug_kernel");
   return out;
 }
 
 // ---------------- host side ----------------
+// EngineDesc pointer <- the tensor of the same name and element type
 #define T_PTR(name, type) S_.name = t_[#name].data_ptr<type>()
-#define T_CPTR(name, type) S_.name = t_[#name].data_ptr<type>()
+// ... for the fields whose pointer type is a same-width alias of the tensor's
+// element type (int64 -> long long / uint64, int8 -> char, f64 rows -> records)
+#define T_ALIAS(name, type) \
+  S_.name = reinterpret_cast<decltype(S_.name)>(t_[#name].data_ptr<type>())
 
 class BatchedSimHip {
  public:
@@ -2391,6 +2351,10 @@ class BatchedSimHip {
     // keep tensor refs alive
     for (auto item : tensors)
       t_[py::cast<std::string>(item.first)] = py::cast<torch::Tensor>(item.second);
+    // optional config key with a default
+    auto opt = [&cfg](const char* key, auto dflt) {
+      return cfg.contains(key) ? cfg[key].cast<decltype(dflt)>() : dflt;
+    };
 
     S_.n_rep = cfg["n_rep"].cast<int>();
     S_.n_dc = cfg["n_dc"].cast<int>();
@@ -2411,7 +2375,7 @@ class BatchedSimHip {
     S_.dvfs_high = cfg["dvfs_high"].cast<double>();
     S_.power_cap = cfg["power_cap"].cast<double>();
     S_.eco_obj = cfg["eco_obj"].cast<int>();
-    S_.fp32_score = cfg.contains("fp32_score") ? cfg["fp32_score"].cast<int>() : 0;
+    S_.fp32_score = opt("fp32_score", 0);
     S_.num_fixed = cfg["num_fixed"].cast<int>();
     S_.fixed_freq = cfg["fixed_freq"].cast<double>();
     S_.payload_gb[0] = cfg["payload_inf_gb"].cast<double>();
@@ -2430,14 +2394,13 @@ class BatchedSimHip {
     S_.cl_cap = cfg["cl_cap"].cast<int>();
     S_.jl_cap = cfg["jl_cap"].cast<int>();
 
-    T_CPTR(freq_levels, double); T_CPTR(pc, double); T_CPTR(lc, double);
-    T_CPTR(wan_lat, double); T_CPTR(wan_bw, double); T_CPTR(carbon, double);
-    T_CPTR(price24, double); T_CPTR(total_gpus, int); T_CPTR(p_idle, double);
-    T_CPTR(p_sleep, double); T_CPTR(p_peak, double); T_CPTR(pow_alpha, double);
-    T_CPTR(power_gating, int); T_CPTR(default_freq, double);
-    T_CPTR(slot_off, int); T_CPTR(slot_dc, int);
-    T_PTR(now, double); T_PTR(next_log, double);
-    S_.rng_ctr = reinterpret_cast<uint64_t*>(t_["rng_ctr"].data_ptr<int64_t>());
+    T_PTR(freq_levels, double); T_PTR(pc, double); T_PTR(lc, double);
+    T_PTR(wan_lat, double); T_PTR(wan_bw, double); T_PTR(carbon, double);
+    T_PTR(price24, double); T_PTR(total_gpus, int); T_PTR(p_idle, double);
+    T_PTR(p_sleep, double); T_PTR(p_peak, double); T_PTR(pow_alpha, double);
+    T_PTR(power_gating, int); T_PTR(default_freq, double);
+    T_PTR(slot_off, int); T_PTR(slot_dc, int);
+    T_PTR(now, double); T_PTR(next_log, double); T_ALIAS(rng_ctr, int64_t);
     T_PTR(jid_ctr, int); T_PTR(done, int); T_PTR(err, int);
     T_PTR(arr_next, double);
     T_PTR(busy, int); T_PTR(cur_freq, double); T_PTR(energy_j, double);
@@ -2445,46 +2408,37 @@ class BatchedSimHip {
     T_PTR(p_active, double); T_PTR(sum_tpt, double); T_PTR(n_running, int);
     T_PTR(dc_min_finish, double); T_PTR(dc_min_slot, int);
     T_PTR(s_finish, double); T_PTR(seq_ctr, int);
-    S_.s_rec = reinterpret_cast<SRec*>(t_["s_rec"].data_ptr<double>());
-    S_.s_gpus = reinterpret_cast<short*>(t_["s_gpus"].data_ptr<int16_t>());
-    S_.s_jtype = reinterpret_cast<char*>(t_["s_jtype"].data_ptr<int8_t>());
-    T_PTR(x_time, double);
-    S_.x_rec = reinterpret_cast<XRec*>(t_["x_rec"].data_ptr<double>());
+    T_ALIAS(s_rec, double); T_PTR(s_gpus, int16_t); T_ALIAS(s_jtype, int8_t);
+    T_PTR(x_time, double); T_ALIAS(x_rec, double);
     T_PTR(q_head, int); T_PTR(q_len, int); T_PTR(q_pay, double);
     if (S_.algo == A_CAP_GREEDY) T_PTR(snap_f, double);
-    T_PTR(q_netlat, float); T_PTR(q_jid, int);
-    S_.q_ing = reinterpret_cast<char*>(t_["q_ing"].data_ptr<int8_t>());
-    T_PTR(b_n, int); T_PTR(b_s, double);
-    S_.b_t = reinterpret_cast<long long*>(t_["b_t"].data_ptr<int64_t>());
-    S_.ev_count = reinterpret_cast<long long*>(t_["ev_count"].data_ptr<int64_t>());
-    S_.jobs_done = reinterpret_cast<long long*>(t_["jobs_done"].data_ptr<int64_t>());
-    S_.jobs_done_inf =
-        reinterpret_cast<long long*>(t_["jobs_done_inf"].data_ptr<int64_t>());
+    T_PTR(q_netlat, float); T_PTR(q_jid, int); T_ALIAS(q_ing, int8_t);
+    T_PTR(b_n, int); T_PTR(b_s, double); T_ALIAS(b_t, int64_t);
+    T_ALIAS(ev_count, int64_t); T_ALIAS(jobs_done, int64_t);
+    T_ALIAS(jobs_done_inf, int64_t);
     T_PTR(sum_lat, double); T_PTR(sum_lat_inf, double); T_PTR(sum_wait, double);
     T_PTR(cl_count, int); T_PTR(cl_rows, double);
     T_PTR(jl_count, int); T_PTR(jl_rows, double);
 
     // arrival-trace replay mode
-    S_.trace_mode = cfg.contains("trace_mode") ? cfg["trace_mode"].cast<int>() : 0;
-    S_.trace_cap = cfg.contains("trace_cap") ? cfg["trace_cap"].cast<int>() : 0;
+    S_.trace_mode = opt("trace_mode", 0);
+    S_.trace_cap = opt("trace_cap", 0);
     if (S_.trace_mode) {
-      T_CPTR(trace_time, double);
-      T_CPTR(trace_size, double);
-      S_.trace_dc = reinterpret_cast<const char*>(t_["trace_dc"].data_ptr<int8_t>());
-      T_PTR(trace_pos, int);
+      T_PTR(trace_time, double); T_PTR(trace_size, double);
+      T_ALIAS(trace_dc, int8_t); T_PTR(trace_pos, int);
     }
 
     // CHSAC-AF extras
-    S_.obs_dim = cfg.contains("obs_dim") ? cfg["obs_dim"].cast<int>() : 0;
-    S_.sla_p99_ms = cfg.contains("sla_p99_ms") ? cfg["sla_p99_ms"].cast<double>() : 500.0;
-    S_.tr_cap = cfg.contains("tr_cap") ? cfg["tr_cap"].cast<int>() : 0;
-    S_.elastic = cfg.contains("elastic") ? cfg["elastic"].cast<int>() : 0;
-    S_.pp_cap = cfg.contains("pp_cap") ? cfg["pp_cap"].cast<int>() : 0;
-    S_.serve_device = cfg.contains("serve_device") ? cfg["serve_device"].cast<int>() : 0;
-    S_.hid = cfg.contains("rl_hid") ? cfg["rl_hid"].cast<int>() : 256;
+    S_.obs_dim = opt("obs_dim", 0);
+    S_.sla_p99_ms = opt("sla_p99_ms", 500.0);
+    S_.tr_cap = opt("tr_cap", 0);
+    S_.elastic = opt("elastic", 0);
+    S_.pp_cap = opt("pp_cap", 0);
+    S_.serve_device = opt("serve_device", 0);
+    S_.hid = opt("rl_hid", 256);
     S_.n_g = S_.max_gpj;
-    S_.rl_det = cfg.contains("rl_det") ? cfg["rl_det"].cast<int>() : 0;
-    S_.tr_limit = cfg.contains("tr_limit") ? cfg["tr_limit"].cast<int>() : 0;
+    S_.rl_det = opt("rl_det", 0);
+    S_.tr_limit = opt("tr_limit", 0);
     if (S_.serve_device) {
       if (S_.hid > RL_MAX_HID || S_.obs_dim > RL_MAX_OBS ||
           S_.n_dc > 8 || S_.n_g > 8)
@@ -2498,36 +2452,23 @@ class BatchedSimHip {
       T_PTR(pend_kind, int); T_PTR(pend_size, double); T_PTR(pend_netlat, float);
       T_PTR(pend_jid, int); T_PTR(pend_ing, int); T_PTR(pend_jt, int);
       T_PTR(pend_dc, int); T_PTR(pend_from_inf, int); T_PTR(pend_enq, double);
-      T_PTR(slot_s0, float);
+      T_PTR(slot_s0, float); T_PTR(x_s0, float);
       T_PTR(pp_count, int); T_PTR(pp_cursor, int);
       T_PTR(pp_size, double); T_PTR(pp_done, double); T_PTR(pp_start, double);
-      T_PTR(pp_netlat, float);
-      T_PTR(pp_jid, int);
-      S_.pp_ing = reinterpret_cast<unsigned char*>(t_["pp_ing"].data_ptr<uint8_t>());
-      S_.pp_dc = reinterpret_cast<unsigned char*>(t_["pp_dc"].data_ptr<uint8_t>());
-      S_.pp_pcount = reinterpret_cast<unsigned char*>(t_["pp_pcount"].data_ptr<uint8_t>());
-      T_PTR(pp_s0, float);
-      S_.pp_adc = reinterpret_cast<unsigned char*>(t_["pp_adc"].data_ptr<uint8_t>());
-      S_.pp_ag = reinterpret_cast<unsigned char*>(t_["pp_ag"].data_ptr<uint8_t>());
-      S_.pp_nrew = reinterpret_cast<unsigned char*>(t_["pp_nrew"].data_ptr<uint8_t>());
-      S_.pp_has_rl = reinterpret_cast<unsigned char*>(t_["pp_has_rl"].data_ptr<uint8_t>());
-      T_PTR(x_s0, float);
-      T_PTR(lat_hist, int);
-      S_.lat_count = reinterpret_cast<long long*>(t_["lat_count"].data_ptr<int64_t>());
-      T_PTR(lat_sum, double);
-      S_.exact_p99 = cfg.contains("exact_p99") ? cfg["exact_p99"].cast<int>() : 0;
-      S_.p99_win = cfg.contains("p99_win") ? cfg["p99_win"].cast<int>() : 2048;
+      T_PTR(pp_netlat, float); T_PTR(pp_jid, int); T_PTR(pp_s0, float);
+      T_PTR(pp_ing, uint8_t); T_PTR(pp_dc, uint8_t); T_PTR(pp_pcount, uint8_t);
+      T_PTR(pp_adc, uint8_t); T_PTR(pp_ag, uint8_t); T_PTR(pp_nrew, uint8_t);
+      T_PTR(pp_has_rl, uint8_t);
+      T_PTR(lat_hist, int); T_ALIAS(lat_count, int64_t); T_PTR(lat_sum, double);
+      S_.exact_p99 = opt("exact_p99", 0);
+      S_.p99_win = opt("p99_win", 2048);
       if (S_.exact_p99) {
-        T_PTR(p99_sorted, double);
-        T_PTR(p99_ring, double);
+        T_PTR(p99_sorted, double); T_PTR(p99_ring, double);
       }
-      T_PTR(tr_count, int);
-      T_PTR(tr_s0, float); T_PTR(tr_s1, float);
-      S_.tr_adc = reinterpret_cast<unsigned char*>(t_["tr_adc"].data_ptr<uint8_t>());
-      S_.tr_ag = reinterpret_cast<unsigned char*>(t_["tr_ag"].data_ptr<uint8_t>());
+      T_PTR(tr_count, int); T_PTR(tr_s0, float); T_PTR(tr_s1, float);
       T_PTR(tr_r, float); T_PTR(tr_costs, float);
-      S_.tr_mdc = reinterpret_cast<unsigned char*>(t_["tr_mdc"].data_ptr<uint8_t>());
-      S_.tr_mg = reinterpret_cast<unsigned char*>(t_["tr_mg"].data_ptr<uint8_t>());
+      T_PTR(tr_adc, uint8_t); T_PTR(tr_ag, uint8_t);
+      T_PTR(tr_mdc, uint8_t); T_PTR(tr_mg, uint8_t);
     }
   }
 
@@ -2538,12 +2479,11 @@ class BatchedSimHip {
   // (the overlapped SAC train kernels) starves behind them — stream
   // priorities cannot help because no slot ever frees.  Masking carves a
   // small CU island the advance never touches; kernels on ordinary streams
-  // land there immediately.
-  void set_resident_cap(bool on) { (void)on; }  // negative result; no-op
-
+  // land there immediately.  (A resident-grid cap on top of the mask was
+  // tried and did not help — see NEGATIVE RESULT above; the uncapped full
+  // grid measured ~20% more events/s.)
   void enable_masked_stream(int n_reserved) {
     if (masked_stream_) return;
-    reserved_cus_ = n_reserved;
     hipDeviceProp_t prop;
     int dev;
     (void)hipGetDevice(&dev);
@@ -2565,16 +2505,10 @@ class BatchedSimHip {
 
   bool masked_active() const { return masked_stream_ != nullptr; }
 
-  bool advance_done() {
-    hipStream_t s = masked_stream_ ? masked_stream_
-                                   : (hipStream_t)at::hip::getCurrentHIPStream();
-    return hipStreamQuery(s) == hipSuccess;
-  }
+  bool advance_done() { return hipStreamQuery(stream()) == hipSuccess; }
 
   void advance_sync() {
-    hipStream_t s = masked_stream_ ? masked_stream_
-                                   : (hipStream_t)at::hip::getCurrentHIPStream();
-    hipError_t e = hipStreamSynchronize(s);
+    hipError_t e = hipStreamSynchronize(stream());
     if (e != hipSuccess)
       throw std::runtime_error(std::string("advance_sync: ") +
                                hipGetErrorString(e));
@@ -2584,60 +2518,44 @@ class BatchedSimHip {
   void advance(double t_target, int64_t max_ev) {
     int rpb = REPLICAS_PER_BLOCK;
     int blocks = (S_.n_rep + rpb - 1) / rpb;
-    // dynamic LDS: per replica, Hot (+ s_finish/x_time mirrors at SUBW==64,
-    // + actor-forward scratch for chsac)
-    size_t hot_sz = (sizeof(Hot) + 15) & ~size_t(15);
-    size_t per_rep = hot_sz;
-    if (SUBW == 64)
-      per_rep += (size_t)S_.total_slots * sizeof(double) +
-                 (size_t)S_.tcap * sizeof(double);
-    if (S_.algo == A_CHSAC)
-      per_rep += (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float);
-    size_t shmem = rpb * per_rep;
+    // one instantiation per Algo, in enum order
+    using AdvanceFn = void (*)(EngineDesc, double, long long);
+    static const AdvanceFn kernels[] = {
+        advance_kernel<A_DEFAULT>, advance_kernel<A_CAP_UNIFORM>,
+        advance_kernel<A_CAP_GREEDY>, advance_kernel<A_JOINT_NF>,
+        advance_kernel<A_BANDIT>, advance_kernel<A_CARBON_COST>,
+        advance_kernel<A_ECO_ROUTE>, advance_kernel<A_DEBUG>,
+        advance_kernel<A_CHSAC>};
+    static_assert(sizeof(kernels) / sizeof(kernels[0]) == A_CHSAC + 1,
+                  "one advance_kernel per Algo");
+    if (S_.algo < 0 || S_.algo > A_CHSAC)
+      throw std::runtime_error("unsupported algo for HIP engine");
+    size_t shmem = rpb * lds_sizes(S_.total_slots, S_.tcap,
+                                   S_.algo == A_CHSAC).stride();
     if (shmem > 64 * 1024)
       throw std::runtime_error(
           "scenario too large for the LDS-mirrored engine (total_slots + "
           "tcap exceed the 64 KiB dynamic-LDS budget per block)");
     dim3 grid(blocks), block(THREADS_PER_BLOCK);
-    hipStream_t stream = masked_stream_
-        ? masked_stream_ : (hipStream_t)at::hip::getCurrentHIPStream();
-    switch (S_.algo) {
-      case A_DEFAULT:
-        hipLaunchKernelGGL(advance_kernel<A_DEFAULT>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_CAP_UNIFORM:
-        hipLaunchKernelGGL(advance_kernel<A_CAP_UNIFORM>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_CAP_GREEDY:
-        hipLaunchKernelGGL(advance_kernel<A_CAP_GREEDY>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_JOINT_NF:
-        hipLaunchKernelGGL(advance_kernel<A_JOINT_NF>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_BANDIT:
-        hipLaunchKernelGGL(advance_kernel<A_BANDIT>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_CARBON_COST:
-        hipLaunchKernelGGL(advance_kernel<A_CARBON_COST>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_ECO_ROUTE:
-        hipLaunchKernelGGL(advance_kernel<A_ECO_ROUTE>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_DEBUG:
-        hipLaunchKernelGGL(advance_kernel<A_DEBUG>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      case A_CHSAC:
-        hipLaunchKernelGGL(advance_kernel<A_CHSAC>, grid, block, shmem, stream, S_, t_target, max_ev); break;
-      default:
-        throw std::runtime_error("unsupported algo for HIP engine");
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-      throw std::runtime_error(std::string("advance_kernel launch failed: ") +
-                               hipGetErrorString(e));
+    hipLaunchKernelGGL(kernels[S_.algo], grid, block, shmem, stream(), S_,
+                       t_target, (long long)max_ev);
+    check_launch("advance_kernel launch failed");
   }
 
  private:
-  EngineDesc S_;
+  // the advance kernel's stream: the CU-masked one once enabled
+  hipStream_t stream() const {
+    return masked_stream_ ? masked_stream_
+                          : (hipStream_t)at::hip::getCurrentHIPStream();
+  }
+
+  EngineDesc S_{};
   std::unordered_map<std::string, torch::Tensor> t_;
   hipStream_t masked_stream_ = nullptr;
-  int reserved_cus_ = 0;
 };
 
 #undef T_PTR
-#undef T_CPTR
+#undef T_ALIAS
 
 }  // namespace dcg
 
@@ -2652,8 +2570,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("enable_masked_stream", &dcg::BatchedSimHip::enable_masked_stream,
            py::arg("n_reserved_cus"))
       .def("masked_active", &dcg::BatchedSimHip::masked_active)
-      .def("set_resident_cap", &dcg::BatchedSimHip::set_resident_cap,
-           py::arg("on"))
       .def("advance_done", &dcg::BatchedSimHip::advance_done)
       .def("advance_sync", &dcg::BatchedSimHip::advance_sync);
   m.def("rl_forward_mfma", &dcg::rl_forward_mfma,

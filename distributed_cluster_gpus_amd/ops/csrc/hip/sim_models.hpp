@@ -45,23 +45,28 @@ __device__ __forceinline__ kc_f64 launch_const(const double* p) { return p; }
 __device__ __forceinline__ kc_i32 launch_const(const int* p) { return p; }
 #endif
 
-// (coefficient-triple pointers are templated: kc_f64 from the engine, plain
-// pointers from anything else)
-template <class P3>
-__device__ __forceinline__ double d_gpu_power(double f, P3 c3) {
-  f = fmax(0.0, f);
-  return c3[0] * f * f * f + c3[1] * f + c3[2];
+// The models are templated on the value type F of the frequency argument:
+// double on the simulation path, float for the opt-in fp32 decision scores
+// (coefficients are read as f64 and narrowed).  Coefficient-triple pointers
+// are templated too: kc_f64 from the engine, plain pointers from anything
+// else.  The narrowed literals are the ones the fp32 scores always used.
+static_assert((float)1e-9 == 1e-9f && (float)3.6e6 == 3.6e6f,
+              "fp32 score literals");
+template <class F, class P3>
+__device__ __forceinline__ F d_gpu_power(F f, P3 c3) {
+  f = fmax((F)0.0, f);
+  return (F)c3[0] * f * f * f + (F)c3[1] * f + (F)c3[2];
 }
-template <class P3>
-__device__ __forceinline__ double d_job_power(int n, double f, P3 c3) {
-  return max(0, n) * d_gpu_power(f, c3);
+template <class F, class P3>
+__device__ __forceinline__ F d_job_power(int n, F f, P3 c3) {
+  return (F)max(0, n) * d_gpu_power(f, c3);
 }
-template <class P3>
-__device__ __forceinline__ double d_unit_time(int n, double f, P3 c3) {
+template <class F, class P3>
+__device__ __forceinline__ F d_unit_time(int n, F f, P3 c3) {
   n = max(1, n);
-  f = fmax(1e-9, f);
-  if (n == 1) return c3[0] + c3[1] / f;
-  return (c3[0] + c3[1] / f + c3[2] * n) / n;
+  f = fmax((F)1e-9, f);
+  if (n == 1) return (F)c3[0] + (F)c3[1] / f;
+  return ((F)c3[0] + (F)c3[1] / f + (F)c3[2] * n) / n;
 }
 
 // ---- subwave reductions ----
@@ -264,110 +269,51 @@ __device__ __forceinline__ int sub_first_empty(const double* row, int lo,
 // scalar scan order (n-major, frequency-minor, first-minimum tie-break) of
 // policies/gridsearch.py::best_nf_grid.
 // objective: 0 energy, 1 carbon (score=E*ci), 2 cost (score=E/3.6e6*price).
+//
+// F is the type the candidates are RANKED in.  float is the opt-in fp32
+// decision score (BASELINE config 5's "fp16/fp32 coeff eval"): only the
+// ranking drops to fp32; the chosen (n, f) feeds the usual f64 time/energy
+// models, so event times and energy integrals keep full precision.  A
+// decision can differ from the f64 path only when two candidates score
+// within fp32 rounding of each other (documented, measurable divergence —
+// off by default).
 struct GridPick { int n; double f, T, P, E; bool found; };
 
-template <class P3, class PF>
+// "no candidate" score per ranking type, and the bound a found score is below
+template <class F> struct ScoreLim;
+template <> struct ScoreLim<double> {
+  static constexpr double none = D_INF, found_below = D_INF;
+};
+template <> struct ScoreLim<float> {
+  static constexpr float none = 3.0e38f;
+  static constexpr double found_below = 3.0e38;
+};
+
+template <class F, class P3, class PF>
 __device__ __forceinline__ GridPick wave_grid_argmin(
     P3 pc3, P3 lc3, PF freq_levels,
     int n_freq, int n_max, int objective, double ci, double price,
     bool has_ddl, double ddl) {
   int lane = sub_lane();
   int n_cand = n_max * n_freq;
-  double best_sc = D_INF;
+  F best_sc = ScoreLim<F>::none;
   int best_ci = INT_MAX;
   for (int cand = lane; cand < n_cand; cand += SUBW) {
     int n = cand / n_freq + 1;
-    double f = freq_levels[cand % n_freq];
-    double T = d_unit_time(n, f, lc3);
-    double E = d_job_power(n, f, pc3) * T;
-    if (has_ddl && T > ddl) continue;
-    double sc = E;
-    if (objective == 1) sc = E * ci;
-    else if (objective == 2) sc = (E / 3.6e6) * price;
-    if (sc < best_sc) { best_sc = sc; best_ci = cand; }
-  }
-  double v;
-  int wi;
-  wave_argmin_idx_f64(best_sc, best_ci, v, wi);
-  GridPick out;
-  out.found = v < D_INF;
-  if (!out.found) {
-    out.n = 1; out.f = 0; out.T = 0; out.P = 0; out.E = 0;
-    return out;
-  }
-  out.n = wi / n_freq + 1;
-  out.f = freq_levels[wi % n_freq];
-  out.T = d_unit_time(out.n, out.f, lc3);
-  out.P = d_job_power(out.n, out.f, pc3);
-  out.E = out.P * out.T;
-  return out;
-}
-
-// energy-argmin over frequencies at fixed n (best_energy_freq),
-// candidate-strided, first-minimum tie-break.
-template <class P3, class PF>
-__device__ __forceinline__ double wave_energy_freq(
-    P3 pc3, P3 lc3, PF freq_levels,
-    int n_freq, int n) {
-  int lane = sub_lane();
-  double best_sc = D_INF;
-  int best_k = INT_MAX;
-  for (int k = lane; k < n_freq; k += SUBW) {
-    double f = freq_levels[k];
-    double sc = d_job_power(n, f, pc3) * d_unit_time(n, f, lc3);
-    if (sc < best_sc) { best_sc = sc; best_k = k; }
-  }
-  double v;
-  int wk;
-  wave_argmin_idx_f64(best_sc, best_k, v, wk);
-  return freq_levels[wk];
-}
-
-// ---- fp32 DECISION-SCORE variants (opt-in, BASELINE config 5's "fp16/fp32
-// coeff eval") ----
-// Only the candidate-ranking math drops to fp32; the chosen (n, f) feeds the
-// usual f64 time/energy models, so event times and energy integrals keep
-// full precision.  A decision can differ from the f64 path only when two
-// candidates score within fp32 rounding of each other (documented,
-// measurable divergence — off by default).
-template <class P3>
-__device__ __forceinline__ float f_gpu_power(float f, P3 c3) {
-  f = fmaxf(0.0f, f);
-  return (float)c3[0] * f * f * f + (float)c3[1] * f + (float)c3[2];
-}
-template <class P3>
-__device__ __forceinline__ float f_unit_time(int n, float f, P3 c3) {
-  n = max(1, n);
-  f = fmaxf(1e-9f, f);
-  if (n == 1) return (float)c3[0] + (float)c3[1] / f;
-  return ((float)c3[0] + (float)c3[1] / f + (float)c3[2] * n) / n;
-}
-
-template <class P3, class PF>
-__device__ __forceinline__ GridPick wave_grid_argmin_f32(
-    P3 pc3, P3 lc3, PF freq_levels,
-    int n_freq, int n_max, int objective, double ci, double price,
-    bool has_ddl, double ddl) {
-  int lane = sub_lane();
-  int n_cand = n_max * n_freq;
-  float best_sc = 3.0e38f;
-  int best_ci = INT_MAX;
-  for (int cand = lane; cand < n_cand; cand += SUBW) {
-    int n = cand / n_freq + 1;
-    float f = (float)freq_levels[cand % n_freq];
-    float T = f_unit_time(n, f, lc3);
-    float E = (float)max(0, n) * f_gpu_power(f, pc3) * T;
-    if (has_ddl && T > (float)ddl) continue;
-    float sc = E;
-    if (objective == 1) sc = E * (float)ci;
-    else if (objective == 2) sc = (E / 3.6e6f) * (float)price;
+    F f = (F)freq_levels[cand % n_freq];
+    F T = d_unit_time(n, f, lc3);
+    F E = d_job_power(n, f, pc3) * T;
+    if (has_ddl && T > (F)ddl) continue;
+    F sc = E;
+    if (objective == 1) sc = E * (F)ci;
+    else if (objective == 2) sc = (E / (F)3.6e6) * (F)price;
     if (sc < best_sc) { best_sc = sc; best_ci = cand; }
   }
   double v;
   int wi;
   wave_argmin_idx_f64((double)best_sc, best_ci, v, wi);
   GridPick out;
-  out.found = v < 3.0e38;
+  out.found = v < ScoreLim<F>::found_below;
   if (!out.found) {
     out.n = 1; out.f = 0; out.T = 0; out.P = 0; out.E = 0;
     return out;
@@ -381,16 +327,18 @@ __device__ __forceinline__ GridPick wave_grid_argmin_f32(
   return out;
 }
 
-template <class P3, class PF>
-__device__ __forceinline__ double wave_energy_freq_f32(
+// energy-argmin over frequencies at fixed n (best_energy_freq),
+// candidate-strided, first-minimum tie-break; ranked in F as above.
+template <class F, class P3, class PF>
+__device__ __forceinline__ double wave_energy_freq(
     P3 pc3, P3 lc3, PF freq_levels,
     int n_freq, int n) {
   int lane = sub_lane();
-  float best_sc = 3.0e38f;
+  F best_sc = ScoreLim<F>::none;
   int best_k = INT_MAX;
   for (int k = lane; k < n_freq; k += SUBW) {
-    float f = (float)freq_levels[k];
-    float sc = (float)max(0, n) * f_gpu_power(f, pc3) * f_unit_time(n, f, lc3);
+    F f = (F)freq_levels[k];
+    F sc = d_job_power(n, f, pc3) * d_unit_time(n, f, lc3);
     if (sc < best_sc) { best_sc = sc; best_k = k; }
   }
   double v;
