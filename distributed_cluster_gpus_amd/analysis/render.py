@@ -29,9 +29,11 @@ def _plt():
 def emit(df: pd.DataFrame, out_dir: str, name: str,
          kind: str = "line", x: Optional[str] = None,
          y=None, title: str = "", ylabel: str = "",
-         hue: Optional[str] = None, logy: bool = False) -> str:
+         hue: Optional[str] = None, logy: bool = False,
+         lo: str = "ci_lo", hi: str = "ci_hi") -> str:
     """Write <name>.csv always; render <name>.png when matplotlib exists.
-    kind: line | bar | hist | scatter | heatmap | box | violin | boxen."""
+    kind: line | band | bar | hist | scatter | heatmap | box | violin | boxen
+    (band: the y line with the [lo, hi] columns shaded around it)."""
     os.makedirs(out_dir, exist_ok=True)
     csv_path = os.path.join(out_dir, f"{name}.csv")
     df.to_csv(csv_path, index=False)
@@ -49,6 +51,14 @@ def emit(df: pd.DataFrame, out_dir: str, name: str,
                 for col in ([y] if isinstance(y, str) else y):
                     ax.plot(df[x], df[col], label=col)
                 ax.legend(fontsize=8)
+            ax.set_xlabel(x)
+        elif kind == "band":
+            for key, sub in (df.groupby(hue) if hue is not None
+                             else [(y, df)]):
+                line, = ax.plot(sub[x], sub[y], label=str(key))
+                ax.fill_between(sub[x], sub[lo], sub[hi], alpha=0.25,
+                                color=line.get_color(), linewidth=0)
+            ax.legend(fontsize=8)
             ax.set_xlabel(x)
         elif kind == "bar":
             ax.bar(df[x].astype(str), df[y])

@@ -40,6 +40,11 @@ _ALGO_IDS = {"default_policy": 0, "cap_uniform": 1, "cap_greedy": 2,
              "debug": 7, "chsac_af": 8}
 _ECO_IDS = {"energy": 0, "carbon": 1, "cost": 2}
 INF = 1e300
+# population-series metrics per DC, in sample-buffer order (PS_K in
+# ops/csrc/hip/pop_series.hpp); the fleet row is named SERIES_FLEET
+SERIES_METRICS = ("freq", "busy", "running", "q_inf", "q_trn", "power_w",
+                  "energy_j")
+SERIES_FLEET = "ALL"
 
 
 class BatchedEngine:
@@ -67,9 +72,13 @@ class BatchedEngine:
                  rl_tr_limit: Optional[int] = None, rl_reserve_cus: int = 16,
                  rl_target_updates_per_s: float = 180.0,
                  tr_cap: int = 262144, arrival_trace=None,
-                 subwave: int = 64, **_unused):
+                 subwave: int = 64,
+                 pop_series: bool = False, pop_series_every: int = 1,
+                 **_unused):
         if algo not in ALGOS:
             raise ValueError(f"unknown algo {algo!r}")
+        if pop_series and int(pop_series_every) < 1:
+            raise ValueError("pop_series_every must be >= 1")
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedEngine requires a ROCm GPU "
                                "(no silent CPU fallback)")
@@ -204,6 +213,29 @@ class BatchedEngine:
         t["cl_rows"] = torch.zeros((cl_cap, 15), **f64)
         t["jl_count"] = torch.zeros(1, **i32)
         t["jl_rows"] = torch.zeros((jl_cap, 11), **f64)
+
+        # population time series (opt-in): every replica snapshots PS_K
+        # metrics per DC plus one fleet row at every pop_series_every-th log
+        # tick.  Launches are bounded by events, so replicas drift apart:
+        # the buffer covers the WHOLE run and is indexed by the per-replica
+        # tick counter ps_tick.  All three live in self.t, so save_state /
+        # load_state carry them and a resumed run continues the series.
+        self.pop_series = bool(pop_series)
+        self.pop_series_every = int(pop_series_every) if self.pop_series else 0
+        if self.pop_series:
+            ps_cap = int(math.ceil(self.end_time / self.log_interval)) \
+                // self.pop_series_every + 2
+            ps_bytes = ps_cap * (n_dc + 1) * len(SERIES_METRICS) * R * 8
+            import logging
+            from ..utils.logging import LOGGER_NAME
+            (logger or logging.getLogger(LOGGER_NAME)).info(
+                f"pop_series: sample buffer {ps_cap} ticks x {n_dc + 1} rows "
+                f"x {len(SERIES_METRICS)} metrics x {R} replicas x 8 B = "
+                f"{ps_bytes} bytes ({ps_bytes / 2**20:.1f} MiB)")
+            t["ps_samples"] = torch.zeros(
+                (ps_cap, n_dc + 1, len(SERIES_METRICS), R), **f64)
+            t["ps_time"] = torch.zeros(ps_cap, **f64)
+            t["ps_tick"] = torch.zeros(R, **i32)
 
         # arrival-trace replay mode (exact single-replica parity testing):
         # arrivals come from a recorded (time, size) FIFO per stream
@@ -409,6 +441,7 @@ class BatchedEngine:
             "tr_limit": getattr(self, "_tr_limit", 0),
             "exact_p99": int(getattr(self, "_exact_p99", False)),
             "p99_win": getattr(self, "_p99_win", 2048),
+            "pop_series_every": self.pop_series_every,
         }
         self._sim = self._mod.BatchedSimHip(t, cfg)
         self.meter = ThroughputMeter()
@@ -895,6 +928,50 @@ class BatchedEngine:
         t = self.t
         return {k: t[k] for k in ("ev_count", "jobs_done", "jobs_done_inf",
                                   "sum_lat", "sum_lat_inf", "energy_j")}
+
+    # ---------------- population time series ----------------
+    def pop_samples(self):
+        """Raw device views of the population time series: ``samples``
+        [T_cap, n_dc+1, K, R] (row n_dc = fleet), ``ticks`` [R] (log ticks
+        each replica has processed) and ``time`` [T_cap] (tick times)."""
+        if not self.pop_series:
+            raise RuntimeError("engine was built without pop_series=True")
+        t = self.t
+        return {"samples": t["ps_samples"], "ticks": t["ps_tick"],
+                "time": t["ps_time"]}
+
+    def population_series(self):
+        """Per-tick statistics over the replica ensemble as a SeriesStats
+        (analysis/montecarlo.py): n, mean, M2, min, max of every sampled
+        metric per DC and fleet-wide, trimmed to the ticks at least one
+        replica has reached.  Valid on an unfinished run (n counts the
+        replicas that reached each tick).  Under torch.distributed the
+        per-rank statistics are merged, so every rank holds the global
+        series."""
+        from ..analysis.montecarlo import SeriesStats, merge_series_stats
+        from ..parallel.dist import allgather_series_stats, is_distributed
+        ps = self.pop_samples()
+        every = self.pop_series_every
+        cap = int(ps["samples"].shape[0])
+        dist_on = self.world > 1 and is_distributed()
+        # ranks must agree on the shape they gather: the full buffer then
+        T = cap if dist_on else min(cap, int(ps["ticks"].max().item()) // every)
+        n_row, K = self.sc.n_dc + 1, len(SERIES_METRICS)
+        raw = self._mod.reduce_series(
+            ps["samples"][:T].view(T, n_row * K, self.R), ps["ticks"], every)
+        names = list(self.sc.dc_names) + [SERIES_FLEET]
+
+        def wrap(flat_stats, time):
+            return SeriesStats.from_tensor(
+                flat_stats.view(T, n_row, K, 5), time,
+                metrics=list(SERIES_METRICS), dc_names=names)
+
+        if not dist_on:
+            return wrap(raw.cpu(), ps["time"][:T].cpu()).trimmed()
+        flat = torch.cat([raw.reshape(-1), ps["time"][:T]])
+        parts = [p.cpu() for p in allgather_series_stats(flat)]
+        return merge_series_stats(
+            [wrap(p[:-T], p[-T:]) for p in parts]).trimmed()
 
     # ---------------- state checkpointing (capability extension) ----------
     def save_state(self, path: str):

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "philox.hpp"
+#include "pop_series.hpp"
 #include "sim_models.hpp"
 
 namespace dcg {
@@ -802,6 +803,53 @@ __device__ void emit_cluster_rows(Ctx& c, double now) {
   }
 }
 
+// population time series: EVERY replica snapshots its per-DC state at the log
+// tick (same place and same expressions as emit_cluster_rows, so a sample
+// equals the matching cl_rows column bit for bit), plus one fleet row summed
+// in DC order 0..n_dc-1 — per-DC variances do not combine into a fleet
+// variance, so the total is sampled per replica.  The replica's own tick
+// counter indexes the buffer (replicas drift apart within a launch).  Cold
+// scattered 8-byte stores, replica-minor for the reduction's coalescing.
+__device__ __forceinline__ void pop_series_sample(Ctx& c,
+                                                  const PopSeriesDesc& P,
+                                                  double now) {
+  const EngineDesc& S = *c.S;
+  int cnt = P.tick[c.r] + 1;
+  if (c.lane == 0) P.tick[c.r] = cnt;
+  if (cnt % P.every == 0) {
+    int ti = cnt / P.every - 1;
+    if (ti < P.t_cap) {
+      const int64_t R = S.n_rep;
+      double* cell = P.samples + (int64_t)ti * (S.n_dc + 1) * PS_K * R + c.r;
+      double acc[PS_K];
+#pragma unroll
+      for (int k = 0; k < PS_K; ++k) acc[k] = 0.0;
+      for (int d = 0; d < S.n_dc; ++d) {
+        const double v[PS_K] = {
+            c.hs->cur_freq[d],         (double)c.hs->busy[d],
+            (double)c.hs->n_running[d], (double)c.hs->q_len[d * 2 + 0],
+            (double)c.hs->q_len[d * 2 + 1], c.dc_power(d),
+            c.hs->energy[d]};
+#pragma unroll
+        for (int k = 0; k < PS_K; ++k) {
+          acc[k] += v[k];
+          if (c.lane == 0) cell[(int64_t)(d * PS_K + k) * R] = v[k];
+        }
+      }
+      acc[0] /= (double)S.n_dc;  // fleet frequency: mean over DCs
+      if (c.lane == 0) {
+#pragma unroll
+        for (int k = 0; k < PS_K; ++k)
+          cell[(int64_t)(S.n_dc * PS_K + k) * R] = acc[k];
+        if (c.r == 0) P.time[ti] = now;
+      }
+    } else if (c.lane == 0) {
+      atomicOr(&S.err[c.r], ERR_LOG_OVF);
+    }
+  }
+  store_fence();
+}
+
 __device__ void emit_job_row(Ctx& c, int d, int jt, int jid, int ing,
                              double size, double fused, int n, float netlat,
                              double start, double finish, int pcount) {
@@ -1487,9 +1535,16 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
 }
 
 // ---------------- the advance kernel ----------------
-template <int ALGO>
+// PS: population-series sampling at the log tick, a compile-time flag so the
+// <ALGO, false> kernels carry none of it.  Its descriptor P is a trailing
+// kernel argument of its own, not a part of EngineDesc: the chsac and
+// cap_greedy kernels keep a copy of EngineDesc in scratch for their
+// out-of-line helpers, and growing it slowed the RL loop measurably
+// (profiles/README.md).
+template <int ALGO, bool PS>
 __global__ void __launch_bounds__(THREADS_PER_BLOCK)
-advance_kernel(EngineDesc S, double t_target, long long max_ev) {
+advance_kernel(EngineDesc S, double t_target, long long max_ev,
+               PopSeriesDesc P) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
   // (64-lane build: the replica index is wave-uniform; say so, so that
@@ -2021,6 +2076,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev) {
       }
       lds_fence();
       emit_cluster_rows(c, t_min);
+      if (PS) pop_series_sample(c, P, t_min);
       if (lane == 0) c.hs->next_log = t_min + S.log_interval;
       lds_fence();
     }
@@ -2470,6 +2526,23 @@ class BatchedSimHip {
       T_PTR(tr_adc, uint8_t); T_PTR(tr_ag, uint8_t);
       T_PTR(tr_mdc, uint8_t); T_PTR(tr_mg, uint8_t);
     }
+
+    // population time series (off unless the host allocated its buffers)
+    ps_.every = opt("pop_series_every", 0);
+    if (ps_.every > 0) {
+      auto& smp = t_["ps_samples"];
+      TORCH_CHECK(smp.dim() == 4 && smp.size(1) == S_.n_dc + 1 &&
+                      smp.size(2) == PS_K && smp.size(3) == S_.n_rep &&
+                      smp.is_contiguous(),
+                  "ps_samples must be [t_cap][n_dc+1][", PS_K, "][n_rep]");
+      ps_.t_cap = (int)smp.size(0);
+      TORCH_CHECK(t_["ps_time"].numel() == ps_.t_cap &&
+                      t_["ps_tick"].numel() == S_.n_rep,
+                  "ps_time must be [t_cap], ps_tick [n_rep]");
+      ps_.samples = smp.data_ptr<double>();
+      ps_.time = t_["ps_time"].data_ptr<double>();
+      ps_.tick = t_["ps_tick"].data_ptr<int>();
+    }
   }
 
   // Create a CU-masked stream for the advance kernel, excluding the LAST
@@ -2518,16 +2591,18 @@ class BatchedSimHip {
   void advance(double t_target, int64_t max_ev) {
     int rpb = REPLICAS_PER_BLOCK;
     int blocks = (S_.n_rep + rpb - 1) / rpb;
-    // one instantiation per Algo, in enum order
-    using AdvanceFn = void (*)(EngineDesc, double, long long);
-    static const AdvanceFn kernels[] = {
-        advance_kernel<A_DEFAULT>, advance_kernel<A_CAP_UNIFORM>,
-        advance_kernel<A_CAP_GREEDY>, advance_kernel<A_JOINT_NF>,
-        advance_kernel<A_BANDIT>, advance_kernel<A_CARBON_COST>,
-        advance_kernel<A_ECO_ROUTE>, advance_kernel<A_DEBUG>,
-        advance_kernel<A_CHSAC>};
-    static_assert(sizeof(kernels) / sizeof(kernels[0]) == A_CHSAC + 1,
-                  "one advance_kernel per Algo");
+    // one instantiation per Algo, in enum order, without and with the
+    // population-series sampling
+    using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc);
+#define DCG_ADVANCE_ROW(PS)                                              \
+  {advance_kernel<A_DEFAULT, PS>,    advance_kernel<A_CAP_UNIFORM, PS>,  \
+   advance_kernel<A_CAP_GREEDY, PS>, advance_kernel<A_JOINT_NF, PS>,     \
+   advance_kernel<A_BANDIT, PS>,     advance_kernel<A_CARBON_COST, PS>,  \
+   advance_kernel<A_ECO_ROUTE, PS>,  advance_kernel<A_DEBUG, PS>,        \
+   advance_kernel<A_CHSAC, PS>}
+    static const AdvanceFn kernels[2][A_CHSAC + 1] = {DCG_ADVANCE_ROW(false),
+                                                      DCG_ADVANCE_ROW(true)};
+#undef DCG_ADVANCE_ROW
     if (S_.algo < 0 || S_.algo > A_CHSAC)
       throw std::runtime_error("unsupported algo for HIP engine");
     size_t shmem = rpb * lds_sizes(S_.total_slots, S_.tcap,
@@ -2537,8 +2612,8 @@ class BatchedSimHip {
           "scenario too large for the LDS-mirrored engine (total_slots + "
           "tcap exceed the 64 KiB dynamic-LDS budget per block)");
     dim3 grid(blocks), block(THREADS_PER_BLOCK);
-    hipLaunchKernelGGL(kernels[S_.algo], grid, block, shmem, stream(), S_,
-                       t_target, (long long)max_ev);
+    hipLaunchKernelGGL(kernels[ps_.samples != nullptr][S_.algo], grid, block,
+                       shmem, stream(), S_, t_target, (long long)max_ev, ps_);
     check_launch("advance_kernel launch failed");
   }
 
@@ -2550,6 +2625,7 @@ class BatchedSimHip {
   }
 
   EngineDesc S_{};
+  PopSeriesDesc ps_{};            // samples == nullptr: feature off
   std::unordered_map<std::string, torch::Tensor> t_;
   hipStream_t masked_stream_ = nullptr;
 };
@@ -2572,6 +2648,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("masked_active", &dcg::BatchedSimHip::masked_active)
       .def("advance_done", &dcg::BatchedSimHip::advance_done)
       .def("advance_sync", &dcg::BatchedSimHip::advance_sync);
+  m.def("reduce_series", &dcg::reduce_series,
+        "population time-series reduction (samples[T,C,R] f64, ticks[R] i32, "
+        "every) -> stats[T,C,5] f64 = {n, mean, M2, min, max}; replica r "
+        "counts at tick t iff ticks[r] / every > t",
+        py::arg("samples"), py::arg("ticks"), py::arg("every"));
   m.def("rl_forward_mfma", &dcg::rl_forward_mfma,
         "MFMA (matrix-core) batched actor forward "
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",

@@ -13,6 +13,9 @@ BASELINE.json:
   bucketed overlap would only pay for multi-hundred-MB gradients.
 * ``allreduce_tensor_sum`` / ``allreduce_scalar`` — replica-shard metric
   reductions (energy totals, latency histograms) for the batched engine.
+* ``allgather_series_stats`` — per-rank population time-series statistics
+  (n / mean / M2 / min / max per tick), merged on every rank by
+  analysis/montecarlo.py::merge_series_stats.
 """
 import os
 from typing import List, Optional
@@ -80,6 +83,18 @@ def allreduce_scalar(x: float, device=None) -> float:
     t = torch.tensor([x], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
     return float(t.item())
+
+
+def allgather_series_stats(stats: torch.Tensor) -> List[torch.Tensor]:
+    """All-gather the flat per-rank population-series statistics (every rank
+    passes the same shape); returns one tensor per rank, in rank order, on
+    every rank.  ``[stats]`` when torch.distributed is not initialized."""
+    if not is_distributed():
+        return [stats]
+    src = stats.detach().contiguous().to(_collective_device())
+    out = [torch.empty_like(src) for _ in range(world_size())]
+    dist.all_gather(out, src)
+    return out
 
 
 def _collective_device() -> torch.device:

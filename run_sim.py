@@ -9,6 +9,8 @@ Extensions over the reference:
   --engine {oracle,native,batched}   pick the scalar Python oracle, the C++
                                      DES core, or the batched MI355X engine
   --replicas N                       Monte-Carlo replicas (batched engine)
+  --pop-series [EVERY]               per-tick mean/CI bands over the replica
+                                     ensemble (batched engine)
   --eco-objective is actually honored (the reference parses but drops it,
     SURVEY Appendix A.4), and --elastic-scaling is a store_true flag that
     really enables elastic scaling (the reference's type=bool flag could
@@ -84,6 +86,12 @@ def parse_args(argv=None):
                         "batched = MI355X HIP replica engine.")
     p.add_argument("--replicas", type=int, default=4096,
                    help="Monte-Carlo replicas (batched engine only).")
+    p.add_argument("--pop-series", type=int, nargs="?", const=1, default=0,
+                   metavar="EVERY",
+                   help="Batched engine only: sample every replica at every "
+                        "EVERY-th log tick and write the per-tick population "
+                        "statistics to <out>/population/population_series.csv "
+                        "(0 = off).")
     p.add_argument("--rl-serve", type=str, default="device",
                    choices=["device", "host"],
                    help="chsac_af policy serving on the batched engine: "
@@ -169,7 +177,10 @@ def main(argv=None):
                             replicas=args.replicas, rl_serve=args.rl_serve,
                             rl_exact_p99=args.rl_exact_p99,
                             rl_target_updates_per_s=args.rl_target_ups,
-                            fp32_coeff_eval=args.fp32_coeff_eval, **common)
+                            fp32_coeff_eval=args.fp32_coeff_eval,
+                            pop_series=args.pop_series > 0,
+                            pop_series_every=max(1, args.pop_series),
+                            **common)
     else:
         from distributed_cluster_gpus_amd.engine.oracle import OracleEngine
         eng = OracleEngine(sc, arrival_inf, arrival_trn, **common)
@@ -189,6 +200,13 @@ def main(argv=None):
             print(f"[population] {rep['replicas']} replicas: total energy "
                   f"{e['mean']:.1f} kJ ± {e['stderr']:.2f} (95% CI "
                   f"[{e['ci_lo']:.1f}, {e['ci_hi']:.1f}])")
+    if args.engine == "batched" and args.pop_series > 0:
+        from distributed_cluster_gpus_amd.analysis.montecarlo import \
+            population_series_report
+        sdf = population_series_report(
+            eng, out_dir=os.path.join(out_dir, "population"))
+        print(f"[population] time series: {sdf['time_s'].nunique()} ticks -> "
+              f"{os.path.join(out_dir, 'population', 'population_series.csv')}")
     if args.rl_checkpoint and getattr(eng, "rl", None) is not None:
         eng.rl.save(args.rl_checkpoint)
         print(f"RL checkpoint saved to {args.rl_checkpoint}")
