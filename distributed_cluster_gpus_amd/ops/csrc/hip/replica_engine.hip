@@ -32,8 +32,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <tuple>
 #include <vector>
 
+#include "launch_plan.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
 #include "sim_models.hpp"
@@ -1541,17 +1544,49 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
 // cap_greedy kernels keep a copy of EngineDesc in scratch for their
 // out-of-line helpers, and growing it slowed the RL loop measurably
 // (profiles/README.md).
-template <int ALGO, bool PS>
-__global__ void __launch_bounds__(THREADS_PER_BLOCK)
+// W: which replicas this launch serves and for how many events each
+// (launch_plan.hpp); a trailing argument of its own for the same reason.
+// WIN: the window arithmetic, a compile-time flag as well: a single launch of
+// all replicas runs the <.., false> kernel, which never looks at W (with the
+// arithmetic always in, the single-launch path measured 0.8 % slower than
+// before; profiles/README.md).  max_ev is the budget of a single launch and
+// W.ev_a of a windowed one.
+// The 8-lane build sits at the 256-VGPR edge of 2 waves/SIMD, where its
+// per-lane replica index and budget offset would tip single instantiations
+// over: hold the register allocator to 2 waves/SIMD there.
+#if DCG_SUBWAVE == 8
+#define DCG_ADVANCE_BOUNDS __launch_bounds__(THREADS_PER_BLOCK, 2)
+#else
+#define DCG_ADVANCE_BOUNDS __launch_bounds__(THREADS_PER_BLOCK)
+#endif
+template <int ALGO, bool PS, bool WIN>
+__global__ void DCG_ADVANCE_BOUNDS
 advance_kernel(EngineDesc S, double t_target, long long max_ev,
-               PopSeriesDesc P) {
+               PopSeriesDesc P, LaunchWindow W) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
-  // (64-lane build: the replica index is wave-uniform; say so, so that
-  // everything indexed by it is scalar address arithmetic)
+  // (64-lane build: the slot, and with it the replica index and the event
+  // budget, is wave-uniform; say so, so that everything indexed by it is
+  // scalar address arithmetic)
   int slot_id = sub_uniform_i32((blockIdx.x * blockDim.x + threadIdx.x) / SUBW);
   int lane = threadIdx.x & (SUBW - 1);
-  if (slot_id >= S.n_rep) return;
+  // chsac always gets the whole ensemble in one launch (its launch cadence
+  // carries meaning)
+  static_assert(!(WIN && ALGO == A_CHSAC), "chsac has no windowed kernel");
+  if (slot_id >= (WIN ? W.count : S.n_rep)) return;
+  // windowed: the event counter runs up to max_ev = W.ev_a for every slot, a
+  // scalar bound in both builds; slots past the split start it at the
+  // difference of the two budgets (the 8-lane build has no registers for a
+  // per-lane bound)
+  long long ev_skip = 0;
+  if (WIN) {
+    slot_id += W.first;
+    if (slot_id >= S.n_rep) slot_id -= S.n_rep;
+    slot_id = sub_uniform_i32(slot_id);
+    ev_skip = sub_uniform_i64(
+        (blockIdx.x * blockDim.x + threadIdx.x) / SUBW >= W.split
+            ? W.ev_a - W.ev_b : 0ll);
+  }
 
   Ctx c;
   c.S = &S;
@@ -1575,7 +1610,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
 
   const int NS = S.n_streams;
   int64_t sbase = (int64_t)c.r * S.total_slots;
-  long long n_events = 0;
+  long long n_events = ev_skip;
   bool paused = false;
   bool skip_loop = false;  // realloc chain pending: bypass the event loop
 
@@ -1672,7 +1707,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
         if (lane == 0) S.pp_cursor[c.r] = nxt;
         store_fence();
         // request the NEXT pool entry and skip straight to the hot-state
-        // writeback (n_events = max_ev empties the event loop; an early
+        // writeback (skip_loop empties the event loop; an early
         // return here would LOSE the LDS-resident bookkeeping updates)
         rl_request_realloc(c, c.now);
         skip_loop = true;
@@ -2117,7 +2152,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
     S.next_log[c.r] = c.hs->next_log;
     S.now[c.r] = c.now;
     S.rng_ctr[c.r] = c.rng.ctr;
-    S.ev_count[c.r] += n_events;
+    S.ev_count[c.r] += n_events - ev_skip;
     S.sum_lat[c.r] = c.hs->sum_lat;
     S.sum_lat_inf[c.r] = c.hs->sum_lat_inf;
     S.sum_wait[c.r] = c.hs->sum_wait;
@@ -2136,6 +2171,11 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
 // spills the wave-uniform scalars, the same failure mode as round 1's
 // noinline experiment.  Train/sim concurrency remains bounded by
 // dispatch behavior; the update-rate controller owns that tradeoff.
+// What the resident-capacity idea was after for the non-chsac engines, a
+// launch that never ends in a thin tail, is done from the host instead:
+// launch_plan.hpp cuts a step into several full launches of this unchanged
+// kernel (BatchedSimHip::advance), which costs the kernel one trailing
+// argument and no loop around its body.
 
 // ---------------- MFMA batched actor forward ----------------
 // Matrix-core path for BATCHED policy evaluation (host-side serving /
@@ -2527,6 +2567,13 @@ class BatchedSimHip {
       T_PTR(tr_mdc, uint8_t); T_PTR(tr_mg, uint8_t);
     }
 
+    // DCG_ADVANCE_PASSES: unset or 0 = plan automatically, 1 = always a
+    // single launch, k = at most k passes
+    if (const char* ev = std::getenv("DCG_ADVANCE_PASSES")) {
+      int k = std::atoi(ev);
+      if (k > 0) max_passes_ = k;
+    }
+
     // population time series (off unless the host allocated its buffers)
     ps_.every = opt("pop_series_every", 0);
     if (ps_.every > 0) {
@@ -2587,34 +2634,79 @@ class BatchedSimHip {
                                hipGetErrorString(e));
   }
 
-  // launch one advance chunk; returns immediately (stream-async)
+  // Launch-plan controls.  resident_capacity 0: ask the runtime (cached);
+  // max_passes 1: always one launch of all replicas, the behaviour before
+  // the planner; min_quantum / launch_cost < 0: the planner's defaults (tests
+  // lower them to cut small budgets too).
+  void set_launch_plan(int resident_capacity, int max_passes,
+                       int64_t min_quantum, int64_t launch_cost) {
+    if (resident_capacity < 0 || max_passes < 1)
+      throw std::runtime_error("set_launch_plan: capacity >= 0, passes >= 1");
+    forced_capacity_ = resident_capacity;
+    max_passes_ = max_passes;
+    min_quantum_ = min_quantum < 0 ? PLAN_MIN_QUANTUM : (long long)min_quantum;
+    launch_cost_ = launch_cost < 0 ? PLAN_LAUNCH_COST : (long long)launch_cost;
+  }
+
+  // replicas the device holds at once: resident blocks per CU at the real
+  // dynamic-LDS size, times CUs, times replicas per block.  Kernel and LDS
+  // size are fixed for the engine's lifetime, so one query serves it.
+  int resident_capacity() {
+    if (forced_capacity_ > 0) return forced_capacity_;
+    if (queried_capacity_ == 0) {
+      int per_cu = 0, dev = 0, n_cu = 0;
+      hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu,
+          reinterpret_cast<const void*>(kernel(S_.algo != A_CHSAC)),
+          THREADS_PER_BLOCK,
+          shmem_bytes());
+      if (e == hipSuccess) e = hipGetDevice(&dev);
+      if (e == hipSuccess)
+        e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount,
+                                  dev);
+      if (e != hipSuccess || per_cu < 1 || n_cu < 1)
+        throw std::runtime_error(std::string("advance occupancy query: ") +
+                                 hipGetErrorString(e));
+      queried_capacity_ = per_cu * n_cu * REPLICAS_PER_BLOCK;
+    }
+    return queried_capacity_;
+  }
+
+  // The launches advance(., max_ev) issues.  One launch of everything for
+  // chsac (its launch cadence carries meaning: tr_limit, pending requests)
+  // and on the CU-masked stream (its capacity is not the device's).
+  LaunchPlan plan_for(long long max_ev) {
+    if (max_passes_ <= 1 || S_.algo == A_CHSAC || masked_stream_) {
+      LaunchPlan p;
+      p.windows.push_back(single_window(S_.n_rep, max_ev));
+      return p;
+    }
+    return make_launch_plan(S_.n_rep, resident_capacity(), max_ev,
+                            max_passes_, min_quantum_, launch_cost_);
+  }
+
+  std::vector<std::tuple<int, int, int, int64_t, int64_t>> launch_plan(
+      int64_t max_ev) {
+    std::vector<std::tuple<int, int, int, int64_t, int64_t>> out;
+    for (const LaunchWindow& w : plan_for(max_ev).windows)
+      out.emplace_back(w.first, w.count, w.split, (int64_t)w.ev_a,
+                       (int64_t)w.ev_b);
+    return out;
+  }
+
+  // enqueue one advance chunk; returns immediately (stream-async)
   void advance(double t_target, int64_t max_ev) {
-    int rpb = REPLICAS_PER_BLOCK;
-    int blocks = (S_.n_rep + rpb - 1) / rpb;
-    // one instantiation per Algo, in enum order, without and with the
-    // population-series sampling
-    using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc);
-#define DCG_ADVANCE_ROW(PS)                                              \
-  {advance_kernel<A_DEFAULT, PS>,    advance_kernel<A_CAP_UNIFORM, PS>,  \
-   advance_kernel<A_CAP_GREEDY, PS>, advance_kernel<A_JOINT_NF, PS>,     \
-   advance_kernel<A_BANDIT, PS>,     advance_kernel<A_CARBON_COST, PS>,  \
-   advance_kernel<A_ECO_ROUTE, PS>,  advance_kernel<A_DEBUG, PS>,        \
-   advance_kernel<A_CHSAC, PS>}
-    static const AdvanceFn kernels[2][A_CHSAC + 1] = {DCG_ADVANCE_ROW(false),
-                                                      DCG_ADVANCE_ROW(true)};
-#undef DCG_ADVANCE_ROW
-    if (S_.algo < 0 || S_.algo > A_CHSAC)
-      throw std::runtime_error("unsupported algo for HIP engine");
-    size_t shmem = rpb * lds_sizes(S_.total_slots, S_.tcap,
-                                   S_.algo == A_CHSAC).stride();
-    if (shmem > 64 * 1024)
-      throw std::runtime_error(
-          "scenario too large for the LDS-mirrored engine (total_slots + "
-          "tcap exceed the 64 KiB dynamic-LDS budget per block)");
-    dim3 grid(blocks), block(THREADS_PER_BLOCK);
-    hipLaunchKernelGGL(kernels[ps_.samples != nullptr][S_.algo], grid, block,
-                       shmem, stream(), S_, t_target, (long long)max_ev, ps_);
-    check_launch("advance_kernel launch failed");
+    const int rpb = REPLICAS_PER_BLOCK;
+    const LaunchPlan plan = plan_for(max_ev);
+    AdvanceFn fn = kernel(plan.windows.size() > 1);
+    size_t shmem = shmem_bytes();
+    dim3 block(THREADS_PER_BLOCK);
+    for (const LaunchWindow& w : plan.windows) {
+      dim3 grid((w.count + rpb - 1) / rpb);
+      hipLaunchKernelGGL(fn, grid, block, shmem, stream(), S_, t_target,
+                         w.ev_a, ps_, w);
+      check_launch("advance_kernel launch failed");
+    }
   }
 
  private:
@@ -2624,8 +2716,52 @@ class BatchedSimHip {
                           : (hipStream_t)at::hip::getCurrentHIPStream();
   }
 
+  using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc,
+                             LaunchWindow);
+
+  // this engine's instantiation: one per Algo, in enum order, without and
+  // with the population-series sampling, without and with the window
+  // arithmetic (chsac: never windowed)
+  AdvanceFn kernel(bool windowed) const {
+#define DCG_ADVANCE_ROW(PS, WIN, CHSAC)                                        \
+  {advance_kernel<A_DEFAULT, PS, WIN>,    advance_kernel<A_CAP_UNIFORM, PS, WIN>, \
+   advance_kernel<A_CAP_GREEDY, PS, WIN>, advance_kernel<A_JOINT_NF, PS, WIN>, \
+   advance_kernel<A_BANDIT, PS, WIN>,     advance_kernel<A_CARBON_COST, PS, WIN>, \
+   advance_kernel<A_ECO_ROUTE, PS, WIN>,  advance_kernel<A_DEBUG, PS, WIN>,    \
+   CHSAC}
+    static const AdvanceFn kernels[2][2][A_CHSAC + 1] = {
+        {DCG_ADVANCE_ROW(false, false, (advance_kernel<A_CHSAC, false, false>)),
+         DCG_ADVANCE_ROW(true, false, (advance_kernel<A_CHSAC, true, false>))},
+        {DCG_ADVANCE_ROW(false, true, nullptr),
+         DCG_ADVANCE_ROW(true, true, nullptr)}};
+#undef DCG_ADVANCE_ROW
+    if (S_.algo < 0 || S_.algo > A_CHSAC)
+      throw std::runtime_error("unsupported algo for HIP engine");
+    AdvanceFn fn = kernels[windowed][ps_.samples != nullptr][S_.algo];
+    if (!fn) throw std::runtime_error("chsac has no windowed advance kernel");
+    return fn;
+  }
+
+  // dynamic LDS of one block
+  size_t shmem_bytes() const {
+    size_t shmem = REPLICAS_PER_BLOCK *
+                   lds_sizes(S_.total_slots, S_.tcap,
+                             S_.algo == A_CHSAC).stride();
+    if (shmem > 64 * 1024)
+      throw std::runtime_error(
+          "scenario too large for the LDS-mirrored engine (total_slots + "
+          "tcap exceed the 64 KiB dynamic-LDS budget per block)");
+    return shmem;
+  }
+
   EngineDesc S_{};
   PopSeriesDesc ps_{};            // samples == nullptr: feature off
+  // launch plan (launch_plan.hpp)
+  int forced_capacity_ = 0;       // 0: the runtime's occupancy answer
+  int queried_capacity_ = 0;      // cache of that answer
+  int max_passes_ = PLAN_MAX_PASSES;
+  long long min_quantum_ = PLAN_MIN_QUANTUM;
+  long long launch_cost_ = PLAN_LAUNCH_COST;
   std::unordered_map<std::string, torch::Tensor> t_;
   hipStream_t masked_stream_ = nullptr;
 };
@@ -2643,6 +2779,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def(py::init<py::dict, py::dict>())
       .def("advance", &dcg::BatchedSimHip::advance,
            py::arg("t_target"), py::arg("max_events"))
+      .def("set_launch_plan", &dcg::BatchedSimHip::set_launch_plan,
+           "resident_capacity 0 = query the runtime; max_passes 1 = single "
+           "launch; min_quantum, launch_cost (events) < 0 = defaults",
+           py::arg("resident_capacity"), py::arg("max_passes"),
+           py::arg("min_quantum") = -1, py::arg("launch_cost") = -1)
+      .def("launch_plan", &dcg::BatchedSimHip::launch_plan,
+           "windows (first, count, split, ev_a, ev_b) advance() would launch",
+           py::arg("max_events"))
+      .def("resident_capacity", &dcg::BatchedSimHip::resident_capacity)
       .def("enable_masked_stream", &dcg::BatchedSimHip::enable_masked_stream,
            py::arg("n_reserved_cus"))
       .def("masked_active", &dcg::BatchedSimHip::masked_active)

@@ -161,6 +161,16 @@ __device__ __forceinline__ int sub_uniform_i32(int x) {
   return x;
 #endif
 }
+// the same for a 64-bit value: two scalar halves
+__device__ __forceinline__ long long sub_uniform_i64(long long x) {
+#if DCG_SUBWAVE == 64
+  unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)x);
+  unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(x >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+#else
+  return x;
+#endif
+}
 
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #if DCG_SUBWAVE == 64
