@@ -456,7 +456,7 @@ class BatchedEngine:
     def _seed_arrivals(self, arrival_inf, arrival_trn, seed, shard):
         """Host-side Philox draws for the initial inter-arrival per stream,
         matching the device recipe (philox.hpp)."""
-        from ._philox_host import philox_u01, replica_key
+        from ._philox_host import philox_u01, replica_key, rexp
         R = shard.count
         NS = self.sc.n_ing * 2
         out = np.full((R, NS), INF)
@@ -475,16 +475,14 @@ class BatchedEngine:
                     ctr += 1
                     continue
                 if arr.mode == "poisson":
-                    u = philox_u01(key, ctr)
-                    out[r, s] = -math.log(1.0 - u) / arr.rate
+                    out[r, s] = rexp(key, ctr, arr.rate)
                     ctr += 1
                 else:  # sinusoid thinning at t=0
                     max_rate = arr.rate * (1.0 + abs(arr.amp))
                     sub = 0
                     ia = INF
                     while sub < 4096:
-                        u1 = philox_u01(key, ctr + ((sub * 2 + 1) << 32))
-                        w = -math.log(1.0 - u1) / max_rate
+                        w = rexp(key, ctr + ((sub * 2 + 1) << 32), max_rate)
                         lam = max(0.0, arr.rate * (1.0 + arr.amp * math.sin(
                             2.0 * math.pi * (w % arr.period) / arr.period)))
                         u2 = philox_u01(key, ctr + ((sub * 2 + 2) << 32))

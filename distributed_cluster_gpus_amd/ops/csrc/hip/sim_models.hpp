@@ -3,8 +3,17 @@
 // The DVFS power polynomial and T(n,f) latency model are fused into every
 // step kernel as inlined device functions ("HIP device
 // function, fused").  f64 forms are used on the simulation path (event times
-// must be BITWISE-equal to the scalar engines; energy integrals need the
-// precision).  The (n,f) grid search is candidate-strided over the replica's
+// must track the scalar engines to rounding; energy integrals need the
+// precision).  They are NOT bitwise-equal to the scalar engines' unfused
+// arithmetic: the extension is compiled with floating-point contraction on,
+// so c0*f*f*f + c1*f + c2 and the c2*n term become FMAs.  Measured through
+// models_debug (tests/test_gpu_models.py): P differs from the unfused f64
+// evaluation on 20 of 500 rows by at most 2 ulp, T on 4 of 500 by 1 ulp; both
+// stay within their rounding depth (6 resp. 4) x 2^-53 of the exact value.
+// Exact score ties between candidates are therefore resolved in DEVICE
+// arithmetic: a contracted score can break a tie the scalar scan sees, or the
+// reverse, whenever two candidates score within that rounding of each other.
+// The (n,f) grid search is candidate-strided over the replica's
 // subgroup: at the default 64-lane width the 8x8 candidate grid maps exactly
 // one-candidate-per-lane onto a CDNA4 wavefront; the
 // 8-lane multi-replica build strides 8 candidates per lane.
