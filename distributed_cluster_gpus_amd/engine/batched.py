@@ -1,7 +1,8 @@
 """BatchedEngine: MI355X Monte-Carlo replica engine orchestrator.
 
 Allocates the replica-major SoA device state (models/scenario tables +
-per-replica simulation state) as torch tensors on the GPU, then drives the
+per-replica simulation state; engine/state.py) as torch tensors on the GPU,
+seeds the arrivals, sets up the RL agent and replay, then drives the
 gfx950 advance kernel (ops/csrc/hip/replica_engine.hip) in chunks until every
 replica reaches end_time.  One wavefront advances one replica; R replicas run
 concurrently.  Memory is sized for 288 GB HBM3E — the default 4096-replica
@@ -29,21 +30,15 @@ import numpy as np
 import torch
 
 from ..models.arrivals import ArrivalProcess
-from ..models.scenario import PAYLOAD_GB, Scenario
+from ..models.scenario import Scenario
 from ..ops import load_sim_hip
 from ..utils.csvlog import ClusterLogWriter, JobLogWriter
 from ..utils.timers import ThroughputMeter
 from .oracle import ALGOS
+from .state import (INF, RL_HID, SERIES_METRICS, alloc_state, engine_cfg,
+                    engine_dims, load_tensors)
 
-_ALGO_IDS = {"default_policy": 0, "cap_uniform": 1, "cap_greedy": 2,
-             "joint_nf": 3, "bandit": 4, "carbon_cost": 5, "eco_route": 6,
-             "debug": 7, "chsac_af": 8}
-_ECO_IDS = {"energy": 0, "carbon": 1, "cost": 2}
-INF = 1e300
-# population-series metrics per DC, in sample-buffer order (PS_K in
-# ops/csrc/hip/pop_series.hpp); the fleet row is named SERIES_FLEET
-SERIES_METRICS = ("freq", "busy", "running", "q_inf", "q_trn", "power_w",
-                  "energy_j")
+# the fleet row of the population series (per-DC rows: SERIES_METRICS)
 SERIES_FLEET = "ALL"
 
 
@@ -103,168 +98,16 @@ class BatchedEngine:
         self.shard = shard
         R = shard.count
         self.R = R
-        n_dc, n_ing, n_freq = scenario.n_dc, scenario.n_ing, scenario.n_freq
-        total_slots = int(scenario.total_gpus.sum())
-        slot_off = np.zeros(n_dc + 1, np.int32)
-        slot_off[1:] = np.cumsum(scenario.total_gpus)
-        slot_dc = np.zeros(total_slots, np.int32)
-        for d in range(n_dc):
-            slot_dc[slot_off[d]:slot_off[d + 1]] = d
-
+        n_dc = scenario.n_dc
+        n_g = int(scenario.policy.max_gpus_per_job)
         dev = self.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        i16 = dict(dtype=torch.int16, device=dev)
-        i8 = dict(dtype=torch.int8, device=dev)
 
-        def T(arr, **kw):
-            return torch.as_tensor(np.ascontiguousarray(arr), **kw).to(dev)
-
-        t = {}
-        # scenario constants
-        t["freq_levels"] = T(scenario.freq_levels, dtype=torch.float64)
-        t["pc"] = T(scenario.power_coeffs.reshape(-1), dtype=torch.float64)
-        t["lc"] = T(scenario.latency_coeffs.reshape(-1), dtype=torch.float64)
-        t["wan_lat"] = T(np.asarray(scenario.wan_latency_s).reshape(-1), dtype=torch.float64)
-        t["wan_bw"] = T(np.asarray(scenario.wan_bottleneck_gbps).reshape(-1), dtype=torch.float64)
-        t["carbon"] = T(scenario.carbon_vec(), dtype=torch.float64)
-        t["price24"] = T(scenario.price_vec24(), dtype=torch.float64)
-        t["total_gpus"] = T(scenario.total_gpus, dtype=torch.int32)
-        t["p_idle"] = T(scenario.p_idle, dtype=torch.float64)
-        t["p_sleep"] = T(scenario.p_sleep, dtype=torch.float64)
-        t["p_peak"] = T([scenario.gpu_specs[n].p_peak for n in scenario.dc_names],
-                        dtype=torch.float64)
-        t["pow_alpha"] = T([scenario.gpu_specs[n].alpha for n in scenario.dc_names],
-                           dtype=torch.float64)
-        t["power_gating"] = T(scenario.power_gating.astype(np.int32), dtype=torch.int32)
-        t["default_freq"] = T(scenario.default_freq, dtype=torch.float64)
-        t["slot_off"] = T(slot_off, dtype=torch.int32)
-        t["slot_dc"] = T(slot_dc, dtype=torch.int32)
-        # per-replica state
-        t["now"] = torch.full((R,), -1.0, **f64)
-        t["next_log"] = torch.full((R,), self.log_interval, **f64)
-        t["rng_ctr"] = torch.zeros(R, **i64)
-        t["jid_ctr"] = torch.zeros(R, **i32)
-        t["done"] = torch.zeros(R, **i32)
-        t["err"] = torch.zeros(R, **i32)
-        t["arr_next"] = torch.full((R, n_ing * 2), INF, **f64)
-        t["busy"] = torch.zeros((R, n_dc), **i32)
-        t["cur_freq"] = torch.empty((R, n_dc), **f64)
-        t["cur_freq"][:] = torch.as_tensor(scenario.default_freq, dtype=torch.float64,
-                                           device=dev)
-        t["energy_j"] = torch.zeros((R, n_dc), **f64)
-        t["util_time"] = torch.zeros((R, n_dc), **f64)
-        t["util_begin"] = torch.full((R, n_dc), -1.0, **f64)
-        t["acc_unit"] = torch.zeros((R, n_dc), **f64)
-        t["p_active"] = torch.zeros((R, n_dc), **f64)
-        t["sum_tpt"] = torch.zeros((R, n_dc), **f64)
-        t["n_running"] = torch.zeros((R, n_dc), **i32)
-        t["dc_min_finish"] = torch.full((R, n_dc), INF, **f64)
-        t["dc_min_slot"] = torch.full((R, n_dc), -1, **i32)
-        t["s_finish"] = torch.full((R, total_slots), INF, **f64)
-        # packed cold slot payload (SRec, 64 B — start/lastupd/size/fused/
-        # done f64, netlat f32, jid/seq i32, ing/pcount/RL-trace bytes);
-        # one cache line per job start/finish instead of 10+ SoA touches
-        t["s_rec"] = torch.zeros((R, total_slots, 8), **f64)
-        t["seq_ctr"] = torch.zeros(R, **i32)
-        t["s_gpus"] = torch.zeros((R, total_slots), **i16)
-        t["s_jtype"] = torch.zeros((R, total_slots), **i8)
-        t["x_time"] = torch.full((R, tcap), INF, **f64)
-        # packed transfer payload (XRec, 32 B)
-        t["x_rec"] = torch.zeros((R, tcap, 4), **f64)
-        t["q_head"] = torch.zeros((R, n_dc, 2), **i32)
-        t["q_len"] = torch.zeros((R, n_dc, 2), **i32)
-        # per-entry (size, enqueue-time) f64 pair — one line per push/pop
-        t["q_pay"] = torch.zeros((R, n_dc, 2, qcap, 2), **f64)
-        # cap_greedy pass-snapshot scratch (frozen task frequencies)
-        t["snap_f"] = torch.zeros(
-            (R, total_slots) if algo == "cap_greedy" else (1, 1), **f64)
-        # queue aux fields (net latency / jid / ingress) are only consumed by
-        # the logging replica's job rows -> single-replica allocation
-        t["q_netlat"] = torch.zeros((n_dc, 2, qcap), **f32)
-        t["q_jid"] = torch.zeros((n_dc, 2, qcap), **i32)
-        t["q_ing"] = torch.zeros((n_dc, 2, qcap), **i8)
-        nb = 1 if algo != "bandit" else R
-        t["b_n"] = torch.zeros((nb, n_dc, 2, n_freq), **i32)
-        t["b_s"] = torch.zeros((nb, n_dc, 2, n_freq), **f64)
-        t["b_t"] = torch.zeros(R, **i64)
-        t["ev_count"] = torch.zeros(R, **i64)
-        t["jobs_done"] = torch.zeros(R, **i64)
-        t["jobs_done_inf"] = torch.zeros(R, **i64)
-        t["sum_lat"] = torch.zeros(R, **f64)
-        t["sum_lat_inf"] = torch.zeros(R, **f64)
-        t["sum_wait"] = torch.zeros(R, **f64)
-
-        # logging buffers (global replica 0 lives on rank 0 shard).  Job rows
-        # are drained chunk-wise between launches (run() copies and resets the
-        # device buffer), so jl_cap bounds only ONE launch's production — the
-        # logging replica emits at most one job row per event, hence
-        # events_per_launch rows per launch — and week-long fully-logged runs
-        # no longer hit ERR_LOG_OVF (round-1 VERDICT item 5 / advisor note).
+        # logging: global replica 0 lives on the rank-0 shard
         self.log_replica = 0 if (enable_logs and shard.start == 0) else -1
-        n_ticks = int(math.ceil(self.end_time / self.log_interval)) + 2
-        cl_cap = (n_dc * n_ticks + 64) if self.log_replica >= 0 else 1
-        jl_cap = max(65536, 2 * self.events_per_launch) \
-            if self.log_replica >= 0 else 1
         self._jl_chunks = []  # host-side drained job-row chunks (np arrays)
-        t["cl_count"] = torch.zeros(1, **i32)
-        t["cl_rows"] = torch.zeros((cl_cap, 15), **f64)
-        t["jl_count"] = torch.zeros(1, **i32)
-        t["jl_rows"] = torch.zeros((jl_cap, 11), **f64)
-
-        # population time series (opt-in): every replica snapshots PS_K
-        # metrics per DC plus one fleet row at every pop_series_every-th log
-        # tick.  Launches are bounded by events, so replicas drift apart:
-        # the buffer covers the WHOLE run and is indexed by the per-replica
-        # tick counter ps_tick.  All three live in self.t, so save_state /
-        # load_state carry them and a resumed run continues the series.
         self.pop_series = bool(pop_series)
         self.pop_series_every = int(pop_series_every) if self.pop_series else 0
-        if self.pop_series:
-            ps_cap = int(math.ceil(self.end_time / self.log_interval)) \
-                // self.pop_series_every + 2
-            ps_bytes = ps_cap * (n_dc + 1) * len(SERIES_METRICS) * R * 8
-            import logging
-            from ..utils.logging import LOGGER_NAME
-            (logger or logging.getLogger(LOGGER_NAME)).info(
-                f"pop_series: sample buffer {ps_cap} ticks x {n_dc + 1} rows "
-                f"x {len(SERIES_METRICS)} metrics x {R} replicas x 8 B = "
-                f"{ps_bytes} bytes ({ps_bytes / 2**20:.1f} MiB)")
-            t["ps_samples"] = torch.zeros(
-                (ps_cap, n_dc + 1, len(SERIES_METRICS), R), **f64)
-            t["ps_time"] = torch.zeros(ps_cap, **f64)
-            t["ps_tick"] = torch.zeros(R, **i32)
-
-        # arrival-trace replay mode (exact single-replica parity testing):
-        # arrivals come from a recorded (time, size) FIFO per stream
         self.trace_mode = arrival_trace is not None
-        if self.trace_mode:
-            # (times, sizes[, routed_dcs]) — routed_dcs entries of -1 let the
-            # algorithm's own routing run (eco_route); >=0 replays the
-            # recorded DC choice (exact-parity for random-routing algos)
-            tt, ts = arrival_trace[0], arrival_trace[1]
-            td = arrival_trace[2] if len(arrival_trace) > 2 else \
-                np.full(np.asarray(tt).shape, -1, np.int8)
-            tt = np.asarray(tt, np.float64)
-            ts = np.asarray(ts, np.float64)
-            td = np.asarray(td, np.int8)
-            assert tt.shape[0] == R and tt.shape[1] == n_ing * 2
-            self.trace_cap = int(tt.shape[2])
-            t["trace_time"] = torch.as_tensor(tt).to(dev)
-            t["trace_size"] = torch.as_tensor(ts).to(dev)
-            t["trace_dc"] = torch.as_tensor(td).to(dev)
-            t["trace_pos"] = torch.zeros((R, n_ing * 2), **i32)
-            t["arr_next"].copy_(t["trace_time"][:, :, 0])
-        else:
-            # seed the initial arrival times on host (one inf + one trn per
-            # ingress per replica), Philox-consistent with the device streams:
-            # the kernel's first draws start at ctr = n_streams; host uses
-            # ctr = stream index for the seed draws.
-            arr_np = self._seed_arrivals(arrival_inf, arrival_trn, seed, shard)
-            t["arr_next"].copy_(torch.as_tensor(arr_np, dtype=torch.float64))
-        t["rng_ctr"].fill_(n_ing * 2)  # host consumed one block per stream
 
         # ===== CHSAC-AF (RL-in-the-loop) =====
         self.is_rl = algo == "chsac_af"
@@ -276,6 +119,7 @@ class BatchedEngine:
         self._rl_train_interval = int(rl_train_interval)
         self._rl_stats_interval = int(rl_stats_interval)
         self._rl_det = bool(rl_deterministic)
+        self._rl_hid = RL_HID
         self.rl_updates = 0
         # serving mode: "device" = the actor MLP + masked Gumbel-max sampling
         # run INSIDE the advance kernel from a flat weights buffer (replicas
@@ -283,6 +127,9 @@ class BatchedEngine:
         # bottleneck); "host" = pause/resume with a batched torch forward
         # (used for parity testing and injected non-standard agents)
         self._serve_device = self.is_rl and rl_serve == "device"
+        # the flat buffer also feeds the MFMA batched forward used by the
+        # host-serving path (matrix-core policy evaluation)
+        self._mfma_serve = False
         self._reserve_cus = int(rl_reserve_cus)
         # overlapped-loop update-rate target: after each advance window the
         # cycle trains serially until the measured SAC update rate meets
@@ -293,64 +140,6 @@ class BatchedEngine:
         # throughput mode -> 5.4M ev/s).
         self._rl_target_ups = float(rl_target_updates_per_s)
         if self.is_rl:
-            t["req_flag"] = torch.zeros(R, **i32)
-            t["req_obs"] = torch.zeros((R, obs_dim), **f32)
-            t["req_mdc"] = torch.zeros(R, **i32)
-            t["req_mg"] = torch.zeros(R, **i32)
-            t["resp_dc"] = torch.zeros(R, **i32)
-            t["resp_g"] = torch.zeros(R, **i32)
-            t["pend_kind"] = torch.zeros(R, **i32)
-            t["pend_size"] = torch.zeros(R, **f64)
-            t["pend_netlat"] = torch.zeros(R, **f32)
-            t["pend_jid"] = torch.zeros(R, **i32)
-            t["pend_ing"] = torch.zeros(R, **i32)
-            t["pend_jt"] = torch.zeros(R, **i32)
-            t["pend_dc"] = torch.zeros(R, **i32)
-            t["pend_from_inf"] = torch.zeros(R, **i32)
-            t["pend_enq"] = torch.zeros(R, **f64)
-            u8 = dict(dtype=torch.uint8, device=dev)
-            # per-job RL obs traces; action/mask bytes live in s_rec/x_rec
-            t["slot_s0"] = torch.zeros((R, total_slots, obs_dim), **f32)
-            t["x_s0"] = torch.zeros((R, tcap, obs_dim), **f32)
-            # elastic-scaling preempted-job pool: a DC can run up to
-            # total_gpus concurrent 1-GPU training jobs, all preemptible
-            pp_cap = int(scenario.total_gpus.max())
-            self._pp_cap = pp_cap
-            u8_ = dict(dtype=torch.uint8, device=dev)
-            t["pp_count"] = torch.zeros(R, **i32)
-            t["pp_cursor"] = torch.zeros(R, **i32)
-            t["pp_size"] = torch.zeros((R, pp_cap), **f64)
-            t["pp_done"] = torch.zeros((R, pp_cap), **f64)
-            t["pp_start"] = torch.zeros((R, pp_cap), **f64)
-            t["pp_netlat"] = torch.zeros((R, pp_cap), **f32)
-            t["pp_jid"] = torch.zeros((R, pp_cap), **i32)
-            t["pp_ing"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_dc"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_pcount"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_s0"] = torch.zeros((R, pp_cap, obs_dim), **f32)
-            t["pp_adc"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_ag"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_nrew"] = torch.zeros((R, pp_cap), **u8_)
-            t["pp_has_rl"] = torch.zeros((R, pp_cap), **u8_)
-            t["lat_hist"] = torch.zeros((R, 2, 64), **i32)
-            t["lat_count"] = torch.zeros((R, 2), **i64)
-            t["lat_sum"] = torch.zeros((R, 2), **f64)
-            # exact sliding-window p99 (parity mode): sorted window + ring
-            # reproducing the reference's np.percentile over 2048 sojourns
-            self._exact_p99 = bool(rl_exact_p99)
-            self._p99_win = 2048
-            p99_shape = (R, 2, self._p99_win) if self._exact_p99 else (1, 1, 1)
-            t["p99_sorted"] = torch.zeros(p99_shape, **f64)
-            t["p99_ring"] = torch.zeros(p99_shape, **f64)
-            t["tr_count"] = torch.zeros(1, **i32)
-            t["tr_s0"] = torch.zeros((tr_cap, obs_dim), **f32)
-            t["tr_s1"] = torch.zeros((tr_cap, obs_dim), **f32)
-            t["tr_adc"] = torch.zeros(tr_cap, **u8)
-            t["tr_ag"] = torch.zeros(tr_cap, **u8)
-            t["tr_r"] = torch.zeros(tr_cap, **f32)
-            t["tr_costs"] = torch.zeros((tr_cap, 3), **f32)
-            t["tr_mdc"] = torch.zeros(tr_cap, **u8)
-            t["tr_mg"] = torch.zeros(tr_cap, **u8)
             # agent + replay on the same device
             from ..rl.agent import CHSACAgentConfig, make_agent
             from ..rl.replay import ReplayRing
@@ -365,93 +154,65 @@ class BatchedEngine:
                 self.rl = rl_agent
             else:
                 self.rl = make_agent(CHSACAgentConfig(
-                    obs_dim=obs_dim, n_dc=n_dc,
-                    n_g_choices=int(scenario.policy.max_gpus_per_job),
+                    obs_dim=obs_dim, n_dc=n_dc, n_g_choices=n_g,
                     constraints=constraints, device=str(dev),
                     graph_capturable=(world == 1)))
             self._graphed = None
             self._use_graph = (world == 1 and rl_agent is None)
             self.replay = ReplayRing(capacity=int(rl_buffer), obs_dim=obs_dim,
                                      n_costs=3, cost_names=self._cost_names,
-                                     n_dc=n_dc,
-                                     n_g=int(scenario.policy.max_gpus_per_job),
+                                     n_dc=n_dc, n_g=n_g,
                                      device=str(dev), seed=seed)
-            # flat fp32 actor-weights buffer for in-kernel serving
-            # (layout documented in replica_engine.hip EngineDesc.pw)
-            n_g = int(scenario.policy.max_gpus_per_job)
-            H = 256
-            servable = self._actor_is_servable(H)
+            servable = self._actor_is_servable(self._rl_hid)
             if self._serve_device and not servable:
                 import warnings
                 warnings.warn("injected agent has non-standard actor dims; "
                               "falling back to host policy serving")
                 self._serve_device = False
-            # the flat buffer also feeds the MFMA batched forward used by
-            # the host-serving path (matrix-core policy evaluation)
             self._mfma_serve = servable and not self._serve_device \
                 and not self._rl_det
-            wsize = (obs_dim * H + H) + 2 * (H * H + H) + (H * H + H) + \
-                (H * n_dc + n_dc) + (H * H + H) + (H * n_g + n_g)
-            t["policy_weights"] = torch.zeros(
-                wsize if (self._serve_device or self._mfma_serve) else 1,
-                **f32)
-            self._rl_hid = H
-            # default yield point: long enough that the overlapped loop can
-            # sustain back-to-back train-graph replays under the advance
-            # window (updates/s stays at the device train rate), short
-            # enough to bound policy staleness to one cycle of transitions
-            self._tr_limit = int(rl_tr_limit) if rl_tr_limit is not None else \
-                min(int(tr_cap) // 2, self._rl_train_interval * 256)
+
+        # device state (engine/state.py): sizes once, then the tensors
+        dims = engine_dims(
+            scenario, algo=algo, n_rep=R, duration=duration,
+            log_interval=log_interval, tcap=tcap, qcap=qcap,
+            events_per_launch=events_per_launch,
+            log_replica=self.log_replica,
+            pop_series_every=self.pop_series_every,
+            arrival_trace=arrival_trace, power_cap=power_cap,
+            eco_objective=eco_objective, fp32_coeff_eval=fp32_coeff_eval,
+            num_fixed_gpus=num_fixed_gpus, fixed_freq=fixed_freq, seed=seed,
+            rep_id_offset=shard.start, sla_p99_ms=sla_p99_ms, tr_cap=tr_cap,
+            elastic_scaling=elastic_scaling, rl_exact_p99=rl_exact_p99,
+            serve_device=self._serve_device, weights_buffer=self._mfma_serve,
+            rl_deterministic=rl_deterministic, rl_tr_limit=rl_tr_limit,
+            rl_train_interval=rl_train_interval)
+        self.dims = dims
+        if self.pop_series:
+            ps_bytes = dims.ps_cap * (n_dc + 1) * len(SERIES_METRICS) * R * 8
+            import logging
+            from ..utils.logging import LOGGER_NAME
+            (logger or logging.getLogger(LOGGER_NAME)).info(
+                f"pop_series: sample buffer {dims.ps_cap} ticks x {n_dc + 1} "
+                f"rows x {len(SERIES_METRICS)} metrics x {R} replicas x 8 B = "
+                f"{ps_bytes} bytes ({ps_bytes / 2**20:.1f} MiB)")
+        t = alloc_state(dims, scenario, dev, arrival_trace)
+        if not self.trace_mode:
+            # seed the initial arrival times on host (one inf + one trn per
+            # ingress per replica), Philox-consistent with the device streams:
+            # the kernel's first draws start at ctr = n_streams; host uses
+            # ctr = stream index for the seed draws.
+            arr_np = self._seed_arrivals(arrival_inf, arrival_trn, seed, shard)
+            t["arr_next"].copy_(torch.as_tensor(arr_np, dtype=torch.float64))
         self.t = t
         self.arrival_inf, self.arrival_trn = arrival_inf, arrival_trn
 
-        cfg = {
-            "n_rep": R, "n_dc": n_dc, "n_ing": n_ing, "n_freq": n_freq,
-            "total_slots": total_slots, "tcap": tcap, "qcap": qcap,
-            "end_time": self.end_time, "log_interval": self.log_interval,
-            "algo": _ALGO_IDS[algo],
-            "max_gpj": int(scenario.policy.max_gpus_per_job),
-            "inf_priority": int(scenario.policy.inf_priority),
-            "scale_out_low": int(scenario.policy.train_scale_out_low_freq),
-            "energy_aware": int(scenario.policy.name == "energy_aware"),
-            "dvfs_low": float(scenario.policy.dvfs_low),
-            "dvfs_high": float(scenario.policy.dvfs_high),
-            "power_cap": float(power_cap),
-            "eco_obj": _ECO_IDS[eco_objective],
-            "fp32_score": int(bool(fp32_coeff_eval)),
-            "num_fixed": int(num_fixed_gpus),
-            "fixed_freq": float(fixed_freq) if fixed_freq else 0.0,
-            "payload_inf_gb": PAYLOAD_GB[0], "payload_trn_gb": PAYLOAD_GB[1],
-            "arr_mode": [self._mode_id(arrival_inf.mode), self._mode_id(arrival_trn.mode)],
-            "arr_rate": [float(arrival_inf.rate), float(arrival_trn.rate)],
-            "arr_amp": [float(arrival_inf.amp), float(arrival_trn.amp)],
-            "arr_period": [float(arrival_inf.period), float(arrival_trn.period)],
-            "seed": int(seed), "rep_id_offset": int(shard.start),
-            "log_replica": self.log_replica,
-            "cl_cap": cl_cap, "jl_cap": jl_cap,
-            "obs_dim": obs_dim, "sla_p99_ms": float(sla_p99_ms),
-            "tr_cap": int(tr_cap) if self.is_rl else 0,
-            "elastic": int(bool(elastic_scaling) and self.is_rl),
-            "pp_cap": getattr(self, "_pp_cap", 0),
-            "trace_mode": int(self.trace_mode),
-            "trace_cap": getattr(self, "trace_cap", 0),
-            "serve_device": int(getattr(self, "_serve_device", False)),
-            "rl_hid": getattr(self, "_rl_hid", 256),
-            "rl_det": int(self._rl_det) if self.is_rl else 0,
-            "tr_limit": getattr(self, "_tr_limit", 0),
-            "exact_p99": int(getattr(self, "_exact_p99", False)),
-            "p99_win": getattr(self, "_p99_win", 2048),
-            "pop_series_every": self.pop_series_every,
-        }
-        self._sim = self._mod.BatchedSimHip(t, cfg)
+        self._sim = self._mod.BatchedSimHip(
+            t, engine_cfg(dims, scenario, arrival_inf, arrival_trn))
         self.meter = ThroughputMeter()
-        if self._serve_device or getattr(self, "_mfma_serve", False):
+        if self._serve_device or self._mfma_serve:
             self._build_weight_refs()
             self._refresh_policy_weights()
-
-    @staticmethod
-    def _mode_id(mode: str) -> int:
-        return {"poisson": 0, "sinusoid": 1, "off": 2}[mode]
 
     def _seed_arrivals(self, arrival_inf, arrival_trn, seed, shard):
         """Host-side Philox draws for the initial inter-arrival per stream,
@@ -582,6 +343,12 @@ class BatchedEngine:
             local_done = int(status[1]) == 1
             t1 = _time.perf_counter()
             tm["advance_s"] += t1 - t0
+            if err != 0 and not dp:
+                # before serving or ingesting anything the overflowed launch
+                # produced (dp: every rank raises together after the sync)
+                raise RuntimeError(
+                    f"batched engine error flags: {err:#x} "
+                    f"(queue/transfer/slot/log overflow)")
             if int(status[4]) >= int(t["jl_rows"].shape[0]) // 2:
                 self._drain_job_rows()
             n_new = 0
@@ -609,10 +376,6 @@ class BatchedEngine:
                 if all_done:
                     break
             else:
-                if err != 0:
-                    raise RuntimeError(
-                        f"batched engine error flags: {err:#x} "
-                        f"(queue/transfer/slot/log overflow)")
                 if self.is_rl:
                     self._tr_backlog += n_new
                     steps = 0
@@ -763,7 +526,7 @@ class BatchedEngine:
                                                 device=self.device)
             t["resp_g"][idx] = torch.as_tensor(gs, dtype=torch.int32,
                                                device=self.device)
-        elif getattr(self, "_mfma_serve", False):
+        elif self._mfma_serve:
             # matrix-core batched forward (rl_forward_mfma) + the same
             # masked Gumbel-max sampling the torch path uses
             from ..rl.masking import sample_categorical
@@ -838,7 +601,7 @@ class BatchedEngine:
                 self.rl.train_step(self.replay.sample(self._rl_batch),
                                    compute_stats=False)
         if refresh and (self._serve_device or
-                        getattr(self, "_mfma_serve", False)):
+                        self._mfma_serve):
             self._refresh_policy_weights()
 
     # ---- in-kernel serving support ----
@@ -986,8 +749,7 @@ class BatchedEngine:
 
     def load_state(self, path: str):
         st = torch.load(path, map_location="cpu", weights_only=False)
-        for k, v in st["tensors"].items():
-            self.t[k].copy_(v.to(self.device))
+        load_tensors(self.t, st["tensors"])
         self.rl_updates = st.get("rl_updates", 0)
         self._jl_chunks = list(st.get("jl_chunks", []))
         if self.rl is not None and st.get("rl") is not None:
@@ -1018,7 +780,10 @@ class BatchedEngine:
         assert torch.equal(run_ref, t["n_running"].long()),             "n_running != active slot count"
         # busy never exceeds capacity; queue lengths within bounds
         assert bool((t["busy"] <= t["total_gpus"].unsqueeze(0)).all()),             "busy > total_gpus"
-        assert bool((t["q_len"] >= 0).all()) and             bool((t["q_len"] < t["q_pay"].shape[-2]).all() or True)
+        # (queue_push refuses at q_len >= qcap, so a full ring holds qcap)
+        assert bool((t["q_len"] >= 0).all()) and \
+            bool((t["q_len"] <= t["q_pay"].shape[-2]).all()), \
+            "q_len outside [0, qcap]"
         # empty slots hold +inf finish; active slots hold finite times
         fin = t["s_finish"]
         assert bool((fin[~active] >= INF).all()), "empty slot with finite finish"

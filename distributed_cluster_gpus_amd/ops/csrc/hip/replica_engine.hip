@@ -33,251 +33,20 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 
+#include "engine_bind.hpp"
+#include "engine_desc.hpp"
+#include "engine_limits.hpp"
 #include "launch_plan.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
 #include "sim_models.hpp"
 
 namespace dcg {
-
-constexpr int MAX_DC = 8;
-constexpr int MAX_FREQ = 8;
-
-// Packed per-object payload records: everything a job start/finish (or a
-// WAN-transfer push/admission) touches lands in ONE cache line instead of
-// 6-12 scattered SoA arrays — the engine is memory-LATENCY-chain bound
-// (profiles/README.md PMC analysis), so dependent line count per event is
-// the cost that matters.  Scan-heavy fields (finish times, gpus, jtype)
-// stay SoA/LDS.
-struct XRec {            // 32 B: in-flight WAN transfer payload
-  double size;
-  float netlat;
-  int jid;
-  short nsel;            // RL-chosen n (chsac; unclamped g+1)
-  unsigned char dc, jtype, ing, adc, ag, mdc;
-  unsigned char mg, has_rl, pad0, pad1;
-};
-static_assert(sizeof(XRec) == 32, "XRec must be one 32B record");
-
-struct SRec {            // 64 B: cold job-slot payload
-  double start, lastupd, size, fused, done;
-  float netlat;
-  int jid;
-  int seq;
-  unsigned char ing, pcount, nrew, adc, ag, mdc, mg, has_rl;
-  unsigned char pad[4];
-};
-static_assert(sizeof(SRec) == 64, "SRec must be one 64B record");
-
-enum Algo { A_DEFAULT = 0, A_CAP_UNIFORM, A_CAP_GREEDY, A_JOINT_NF, A_BANDIT,
-            A_CARBON_COST, A_ECO_ROUTE, A_DEBUG, A_CHSAC };
-
-// CHSAC-AF action-request state machine kinds
-enum PendKind : int { PEND_NONE = 0, PEND_ARRIVAL = 1, PEND_DRAIN = 2,
-                      PEND_REALLOC = 3 };
-// request flags
-enum ReqFlag : int { REQ_IDLE = 0, REQ_PENDING = 1, REQ_READY = 2 };
-
-constexpr int LAT_BINS = 64;  // log10 bins over sojourn [1e-4 s, 1e4 s)
-
-enum Err : int { ERR_NONE = 0, ERR_QUEUE_OVF = 1, ERR_XFER_OVF = 2,
-                 ERR_SLOT_OVF = 4, ERR_LOG_OVF = 8 };
-
-struct EngineDesc {
-  // sizes
-  int n_rep, n_dc, n_ing, n_freq, n_streams, total_slots, tcap, qcap;
-  double end_time, log_interval;
-  // scenario constants (device)
-  const double* freq_levels;      // [n_freq]
-  const double* pc;               // [dc][2][3]
-  const double* lc;               // [dc][2][3]
-  const double* wan_lat;          // [ing][dc]
-  const double* wan_bw;           // [ing][dc]
-  const double* carbon;           // [dc]
-  const double* price24;          // [24]
-  const int* total_gpus;          // [dc]
-  const double* p_idle;           // [dc]
-  const double* p_sleep;          // [dc]
-  const double* p_peak;           // [dc] (baseline end-flush model)
-  const double* pow_alpha;        // [dc]
-  const int* power_gating;        // [dc]
-  const double* default_freq;     // [dc]
-  const int* slot_off;            // [dc+1]
-  const int* slot_dc;             // [total_slots] slot -> dc
-  // policy / run params
-  int algo, max_gpj, inf_priority, scale_out_low, energy_aware;
-  double dvfs_low, dvfs_high, power_cap;
-  int eco_obj, num_fixed;
-  int fp32_score;                 // opt-in fp32 decision-score eval (grid /
-                                  //   energy-freq argmins; times stay f64)
-  double fixed_freq;
-  double payload_gb[2];
-  // arrival processes by jtype: mode 0=poisson 1=sinusoid 2=off
-  int arr_mode[2];
-  double arr_rate[2], arr_amp[2], arr_period[2];
-  uint64_t seed;
-  int64_t rep_id_offset;          // global replica id of local replica 0
-  // per-replica scalars
-  double* now;                    // [r] (last event time; <0 = no event yet)
-  double* next_log;               // [r]
-  uint64_t* rng_ctr;              // [r]
-  int* jid_ctr;                   // [r]
-  int* done;                      // [r]
-  int* err;                       // [r]
-  double* arr_next;               // [r][n_streams]  (stream = ing*2 + jtype)
-  // per (r, dc)
-  int* busy;
-  double* cur_freq;
-  double* energy_j;
-  double* util_time;
-  double* util_begin;             // [r][dc] first-event stamp (<0 unset)
-  double* acc_unit;
-  double* p_active;               // cached sum of running-job powers
-  double* sum_tpt;                // cached sum of running-job throughputs
-  int* n_running;
-  double* dc_min_finish;          // cached min finish time (INF if none)
-  int* dc_min_slot;
-  // job slots [r][total_slots]: finish times + scan fields SoA, the cold
-  // payload as one SRec per slot (f64 values bitwise-exact as before)
-  double* s_finish;               // INF = empty
-  SRec* s_rec;                    // packed payload
-  short* s_gpus;                  // 0 = empty (dense busy/log scans)
-  char* s_jtype;                  // dense scans (log rows, elastic, cap)
-  // in-flight transfers [r][tcap]: time SoA (LDS-mirrored), payload packed
-  double* x_time;                 // INF = empty
-  XRec* x_rec;
-  // queues [r][dc][2] ring of capacity qcap; per-entry payload = (size,
-  // enqueue-time) f64 pair; aux fields (netlat/jid/ing) exist only for the
-  // logging replica ([dc][2][qcap], no replica dim)
-  int* q_head;
-  int* q_len;
-  double* q_pay;                  // [r][dc][2][qcap][2] (f64 exact parity)
-  float* q_netlat;                // [dc][2][qcap] (log replica only)
-  int* q_jid;                     // [dc][2][qcap] (log replica only)
-  char* q_ing;                    // [dc][2][qcap] (log replica only)
-  // bandit state [r][dc][2][n_freq]
-  int* b_n;
-  double* b_s;
-  long long* b_t;                 // [r]
-  // metrics [r]
-  long long* ev_count;
-  long long* jobs_done;
-  long long* jobs_done_inf;
-  double* sum_lat;
-  double* sum_lat_inf;
-  double* sum_wait;               // summed queueing delay (job start minus
-                                  //   its enqueue at the DC; 0 for jobs that
-                                  //   start straight off the WAN transfer)
-  int* seq_ctr;                   // [r] job-start sequence counter
-  double* snap_f;                 // [r][total_slots] cap_greedy pass snapshot
-                                  //   (allocated only for algo==cap_greedy)
-  // logging (one designated replica); the host drains both buffers
-  // chunk-wise between launches, so caps bound one launch's production only
-  int log_replica;                // -1 = off
-  int cl_cap, jl_cap;
-  int* cl_count;                  // [1]
-  double* cl_rows;                // [cl_cap][15]
-  int* jl_count;                  // [1]
-  double* jl_rows;                // [jl_cap][11]
-  // ===== arrival-trace replay mode (single-replica exact-parity testing:
-  // arrivals come from a host-recorded (time, size) FIFO per stream instead
-  // of the Philox draws) =====
-  int trace_mode;                 // 0 off, 1 on
-  int trace_cap;                  // entries per stream
-  const double* trace_time;       // [r][n_streams][cap] absolute times
-  const double* trace_size;       // [r][n_streams][cap]
-  const char* trace_dc;           // [r][n_streams][cap] routed DC (-1 = use
-                                  //   the algorithm's own routing)
-  int* trace_pos;                 // [r][n_streams] cursor
-  // ===== CHSAC-AF (RL-in-the-loop) state; null unless algo == A_CHSAC =====
-  int obs_dim;                    // 1 + 6*n_dc
-  double sla_p99_ms;
-  // --- device-side policy serving (serve_device=1): the actor MLP runs
-  // INSIDE the advance kernel from a flat weights buffer the host refreshes
-  // after each SAC train round, so replicas never pause for a host policy
-  // round-trip (round-1 bottleneck: 206k ev/s host-loop-bound).  Layout of
-  // pw (all fp32, [in][out]-major so the out index is lane-coalesced):
-  //   enc1 Wt[obs_dim][hid] b[hid] | enc2 Wt[hid][hid] b | enc3 Wt[hid][hid] b
-  //   | hdc1 Wt[hid][hid] b | hdc2 Wt[hid][n_dc] b[n_dc]
-  //   | hg1 Wt[hid][hid] b | hg2 Wt[hid][n_g] b[n_g]
-  int serve_device;               // 0 = host pause/resume, 1 = in-kernel
-  int hid;                        // encoder/head hidden width (<= RL_MAX_HID)
-  int n_g;                        // g-head size (max_gpj)
-  int rl_det;                     // 1 = greedy argmax (no Gumbel draw)
-  int tr_limit;                   // yield the launch when the transition ring
-                                  //   reaches this (bounds policy staleness)
-  const float* pw;                // flat policy weights
-  // action request/response, one slot per replica
-  int* req_flag;                  // [r] ReqFlag
-  float* req_obs;                 // [r][obs_dim]
-  int* req_mdc;                   // [r] bitmask of valid DCs
-  int* req_mg;                    // [r] bitmask of valid g choices
-  int* resp_dc;                   // [r]
-  int* resp_g;                    // [r]
-  int* pend_kind;                 // [r] PendKind
-  // stashed context for the paused event
-  double* pend_size;              // [r]
-  float* pend_netlat;             // [r]
-  int* pend_jid;                  // [r]
-  int* pend_ing;                  // [r]
-  int* pend_jt;                   // [r]
-  int* pend_dc;                   // [r] (drain: source DC)
-  int* pend_from_inf;             // [r] (drain: 1 = popped from the inference
-                                  //   queue; kept for the host-side state
-                                  //   layout — the resume reads pend_jt)
-  double* pend_enq;               // [r] (drain: the popped job's enqueue time)
-  // per-job RL obs traces (the action/mask bytes live in SRec/XRec;
-  // arrival path keeps nrew = g_idx+1 unclamped, drain path clamped —
-  // reference :571 vs :889)
-  float* slot_s0;                 // [r][total_slots][obs_dim]
-  float* x_s0;                    // [r][tcap][obs_dim]
-  // elastic scaling (chsac only): preempted-training-job pool per replica
-  int elastic;                    // 0 off, 1 on
-  int pp_cap;                     // pool capacity
-  int* pp_count;                  // [r] entries in pool
-  int* pp_cursor;                 // [r] next entry to reallocate
-  double* pp_size;                // [r][cap] original size
-  double* pp_done;                // [r][cap] units completed at preemption
-  double* pp_start;               // [r][cap] ORIGINAL start time (resume
-                                  //   keeps it: latency spans preemptions)
-  float* pp_netlat;               // [r][cap]
-  int* pp_jid;                    // [r][cap]
-  unsigned char* pp_ing;          // [r][cap]
-  unsigned char* pp_dc;           // [r][cap]
-  unsigned char* pp_pcount;       // [r][cap] job's preempt count
-  float* pp_s0;                   // [r][cap][obs_dim] carried RL trace
-  unsigned char* pp_adc;          // [r][cap]
-  unsigned char* pp_ag;           // [r][cap]
-  unsigned char* pp_nrew;         // [r][cap]
-  unsigned char* pp_has_rl;       // [r][cap]
-  // latency histograms per (r, jtype): counts in log10 bins
-  int* lat_hist;                  // [r][2][LAT_BINS]
-  long long* lat_count;           // [r][2]
-  double* lat_sum;                // [r][2]
-  // exact sliding-window p99 (parity mode): the reference computes an exact
-  // percentile over the last 2048 sojourns (simulator_paper_multi.py:728-737)
-  // where the fast path approximates from the log histogram.  exact_p99=1
-  // maintains a SORTED window + an insertion-order ring per (r, jtype) and
-  // reproduces np.percentile(buf, 99) bit-for-bit.
-  int exact_p99;
-  int p99_win;                    // window size (2048)
-  double* p99_sorted;             // [r][2][win]
-  double* p99_ring;               // [r][2][win]
-  // transition ring (global across replicas; host drains between launches)
-  int tr_cap;
-  int* tr_count;                  // [1] atomicAdd cursor
-  float* tr_s0;                   // [cap][obs_dim]
-  float* tr_s1;                   // [cap][obs_dim]
-  unsigned char* tr_adc;          // [cap]
-  unsigned char* tr_ag;           // [cap]
-  float* tr_r;                    // [cap]
-  float* tr_costs;                // [cap][3]: latency_p99_ms, power_W, gpu_over
-  unsigned char* tr_mdc;          // [cap]
-  unsigned char* tr_mg;           // [cap]
-};
 
 // ---------------- wave helpers ----------------
 // (the subgroup reductions live in sim_models.hpp)
@@ -299,7 +68,6 @@ __device__ __forceinline__ void lds_fence() {
 // and are written back to HBM at kernel exit.  This removes most of the
 // dependent global-memory round trips per event (PMC before: waves waiting
 // 63% of cycles on memory; see profiles/README.md).
-constexpr int MAX_STREAMS = 16;
 constexpr int THREADS_PER_BLOCK = 128;
 constexpr int REPLICAS_PER_BLOCK = THREADS_PER_BLOCK / DCG_SUBWAVE;
 struct Hot {
@@ -325,9 +93,6 @@ struct Hot {
   int q_head[MAX_DC * 2];
 };
 
-constexpr int RL_MAX_HID = 256;
-constexpr int RL_MAX_OBS = 64;
-constexpr int RL_MAX_LOG = 16;
 // actor-forward LDS scratch: obs, two activation buffers, head logits
 constexpr size_t RL_LDS_BYTES =
     (RL_MAX_OBS + 2 * RL_MAX_HID + RL_MAX_LOG) * sizeof(float);
@@ -2318,427 +2083,14 @@ std::vector<torch::Tensor> rl_forward_mfma(torch::Tensor pw,
   return {out_dc, out_g};
 }
 
-// standalone batched actor forward (test/verification path): one subwave
-// slot per observation row, same device math as the in-engine serving
-__global__ void __launch_bounds__(THREADS_PER_BLOCK)
-rl_forward_kernel(const float* pw, const float* obs, int B, int obs_dim,
-                  int hid, int n_dc, int n_g, float* out_dc, float* out_g) {
-  int slot = (blockIdx.x * blockDim.x + threadIdx.x) / SUBW;
-  int lane = threadIdx.x & (SUBW - 1);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* rb =
-      reinterpret_cast<float*>(smem + (threadIdx.x / SUBW) * RL_LDS_BYTES);
-  if (slot >= B) return;
-  float* l_obs = rb;
-  float* A = rb + RL_MAX_OBS;
-  float* Bv = A + RL_MAX_HID;
-  float* L = Bv + RL_MAX_HID;
-  for (int k = lane; k < obs_dim; k += SUBW)
-    l_obs[k] = obs[(int64_t)slot * obs_dim + k];
-  lds_fence();
-  rl_logits_impl(pw, obs_dim, hid, n_dc, n_g, l_obs, A, Bv, L, lane);
-  for (int k = lane; k < n_dc; k += SUBW)
-    out_dc[(int64_t)slot * n_dc + k] = L[k];
-  for (int k = lane; k < n_g; k += SUBW)
-    out_g[(int64_t)slot * n_g + k] = L[8 + k];
-}
+}  // namespace dcg
 
-std::vector<torch::Tensor> rl_forward_debug(torch::Tensor pw,
-                                            torch::Tensor obs,
-                                            int64_t hid, int64_t n_dc,
-                                            int64_t n_g) {
-  TORCH_CHECK(pw.is_cuda() && obs.is_cuda() && pw.dtype() == torch::kFloat32);
-  int B = obs.size(0), D = obs.size(1);
-  auto out_dc = torch::empty({B, n_dc}, obs.options());
-  auto out_g = torch::empty({B, n_g}, obs.options());
-  int rpb = REPLICAS_PER_BLOCK;
-  int blocks = (B + rpb - 1) / rpb;
-  size_t shmem = (size_t)rpb * RL_LDS_BYTES;
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(rl_forward_kernel, dim3(blocks), dim3(THREADS_PER_BLOCK),
-                     shmem, stream, pw.data_ptr<float>(),
-                     obs.data_ptr<float>(), B, D, (int)hid, (int)n_dc,
-                     (int)n_g, out_dc.data_ptr<float>(),
-                     out_g.data_ptr<float>());
-  check_launch("rl_forward_kernel");
-  return {out_dc, out_g};
-}
+// test-only entry points (their kernels and bindings)
+#include "debug_entries.hpp"
 
-// standalone drivers for the subgroup reduction helpers (test/verification
-// path): one wavefront per row runs the production device functions
-__global__ void __launch_bounds__(64)
-wave_reduce_debug_kernel(const double* vals, const int* idx, double* v_lane,
-                         int* o_lane, double* v_idx, int* o_idx) {
-  int64_t row = blockIdx.x;
-  int lane = threadIdx.x;
-  double x = vals[row * 64 + lane];
-  int ix = idx[row * 64 + lane];
-  int wl;
-  double a = wave_argmin_f64(x, wl);
-  double b;
-  int bi;
-  wave_argmin_idx_f64(x, ix, b, bi);
-  if (lane == 0) {
-    v_lane[row] = a;
-    o_lane[row] = wl;
-    v_idx[row] = b;
-    o_idx[row] = bi;
-  }
-}
-
-std::vector<torch::Tensor> wave_reduce_debug(torch::Tensor vals,
-                                             torch::Tensor idx) {
-  TORCH_CHECK(SUBW == 64, "wave_reduce_debug drives the 64-lane reductions");
-  TORCH_CHECK(vals.is_cuda() && idx.is_cuda() &&
-              vals.dtype() == torch::kFloat64 && idx.dtype() == torch::kInt32);
-  TORCH_CHECK(vals.dim() == 2 && vals.size(1) == 64 &&
-              idx.sizes() == vals.sizes());
-  vals = vals.contiguous();
-  idx = idx.contiguous();
-  int64_t B = vals.size(0);
-  auto v_lane = torch::empty({B}, vals.options());
-  auto o_lane = torch::empty({B}, idx.options());
-  auto v_idx = torch::empty({B}, vals.options());
-  auto o_idx = torch::empty({B}, idx.options());
-  if (B == 0) return {v_lane, o_lane, v_idx, o_idx};
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(wave_reduce_debug_kernel, dim3((unsigned)B), dim3(64), 0,
-                     stream, vals.data_ptr<double>(), idx.data_ptr<int>(),
-                     v_lane.data_ptr<double>(), o_lane.data_ptr<int>(),
-                     v_idx.data_ptr<double>(), o_idx.data_ptr<int>());
-  check_launch("wave_reduce_debug_kernel");
-  return {v_lane, o_lane, v_idx, o_idx};
-}
-
-__global__ void __launch_bounds__(64)
-first_empty_debug_kernel(const double* rows, int L, int* out) {
-  int64_t row = blockIdx.x;
-  int k = sub_first_empty(rows + row * L, 0, L);
-  if (threadIdx.x == 0) out[row] = k;
-}
-
-torch::Tensor first_empty_debug(torch::Tensor rows) {
-  TORCH_CHECK(rows.is_cuda() && rows.dtype() == torch::kFloat64 &&
-              rows.dim() == 2 && rows.size(1) >= 1 &&
-              rows.size(1) < (1 << 30));
-  rows = rows.contiguous();
-  int64_t B = rows.size(0);
-  auto out = torch::empty({B}, rows.options().dtype(torch::kInt32));
-  if (B == 0) return out;
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(first_empty_debug_kernel, dim3((unsigned)B), dim3(64), 0,
-                     stream, rows.data_ptr<double>(), (int)rows.size(1),
-                     out.data_ptr<int>());
-  check_launch("first_empty_debug_kernel");
-  return out;
-}
-
-// standalone drivers for the RNG (philox.hpp) and the analytic models / grid
-// searches (sim_models.hpp), same test/verification path.  The RNG and model
-// drivers run one thread per row; the grid drivers one 64-thread block per
-// row (8-lane build: every subgroup solves the same row, subgroup 0 writes).
-constexpr int RNG_DRAW_COLS = 7;  // u01, u01x2 a, u01x2 b, rexp, rnormal,
-                                  // rlognormal, rpareto_inf
-constexpr int RNG_CTR_COLS = 7;   // u01, u01x2, rexp, rbelow, rnormal,
-                                  // rlognormal, rpareto_inf
-
-__global__ void __launch_bounds__(64)
-philox_debug_kernel(const int64_t* keys, const int64_t* ctrs, int64_t B,
-                    int64_t* words) {
-  int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= B) return;
-  uint32_t w[4];
-  philox4x32((uint64_t)keys[row], (uint64_t)ctrs[row], w);
-  for (int k = 0; k < 4; ++k) words[row * 4 + k] = (int64_t)w[k];
-}
-
-torch::Tensor philox_debug(torch::Tensor keys, torch::Tensor ctrs) {
-  TORCH_CHECK(keys.is_cuda() && ctrs.is_cuda() &&
-              keys.dtype() == torch::kInt64 && ctrs.dtype() == torch::kInt64);
-  TORCH_CHECK(keys.dim() == 1 && ctrs.sizes() == keys.sizes());
-  keys = keys.contiguous();
-  ctrs = ctrs.contiguous();
-  int64_t B = keys.size(0);
-  auto words = torch::empty({B, 4}, keys.options());
-  if (B == 0) return words;
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(philox_debug_kernel, dim3((unsigned)((B + 63) / 64)),
-                     dim3(64), 0, stream, keys.data_ptr<int64_t>(),
-                     ctrs.data_ptr<int64_t>(), B, words.data_ptr<int64_t>());
-  check_launch("philox_debug_kernel");
-  return words;
-}
-
-// every production draw from a fresh state at (key, ctr): the value and the
-// counter the draw leaves behind
-__global__ void __launch_bounds__(64)
-rng_draws_debug_kernel(const int64_t* keys, const int64_t* ctrs,
-                       const int64_t* n_below, int64_t B, double lambd,
-                       double mu, double sigma, double* vals, int64_t* below,
-                       int64_t* ctr_after) {
-  int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= B) return;
-  double* v = vals + row * RNG_DRAW_COLS;
-  int64_t* ca = ctr_after + row * RNG_CTR_COLS;
-  auto fresh = [&]() {
-    return PhiloxState{(uint64_t)keys[row], (uint64_t)ctrs[row]};
-  };
-  PhiloxState st = fresh();
-  v[0] = u01(st);
-  ca[0] = (int64_t)st.ctr;
-  st = fresh();
-  u01x2(st, v[1], v[2]);
-  ca[1] = (int64_t)st.ctr;
-  st = fresh();
-  v[3] = rexp(st, lambd);
-  ca[2] = (int64_t)st.ctr;
-  st = fresh();
-  below[row] = (int64_t)rbelow(st, (uint32_t)n_below[row]);
-  ca[3] = (int64_t)st.ctr;
-  st = fresh();
-  v[4] = rnormal(st, mu, sigma);
-  ca[4] = (int64_t)st.ctr;
-  st = fresh();
-  v[5] = rlognormal(st, mu, sigma);
-  ca[5] = (int64_t)st.ctr;
-  st = fresh();
-  v[6] = rpareto_inf(st);
-  ca[6] = (int64_t)st.ctr;
-}
-
-std::vector<torch::Tensor> rng_draws_debug(torch::Tensor keys,
-                                           torch::Tensor ctrs,
-                                           torch::Tensor n_below, double lambd,
-                                           double mu, double sigma) {
-  TORCH_CHECK(keys.is_cuda() && ctrs.is_cuda() && n_below.is_cuda() &&
-              keys.dtype() == torch::kInt64 && ctrs.dtype() == torch::kInt64 &&
-              n_below.dtype() == torch::kInt64);
-  TORCH_CHECK(keys.dim() == 1 && ctrs.sizes() == keys.sizes() &&
-              n_below.sizes() == keys.sizes());
-  keys = keys.contiguous();
-  ctrs = ctrs.contiguous();
-  n_below = n_below.contiguous();
-  int64_t B = keys.size(0);
-  auto vals = torch::empty({B, RNG_DRAW_COLS},
-                           keys.options().dtype(torch::kFloat64));
-  auto below = torch::empty({B}, keys.options());
-  auto ctr_after = torch::empty({B, RNG_CTR_COLS}, keys.options());
-  if (B == 0) return {vals, below, ctr_after};
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(rng_draws_debug_kernel, dim3((unsigned)((B + 63) / 64)),
-                     dim3(64), 0, stream, keys.data_ptr<int64_t>(),
-                     ctrs.data_ptr<int64_t>(), n_below.data_ptr<int64_t>(), B,
-                     lambd, mu, sigma, vals.data_ptr<double>(),
-                     below.data_ptr<int64_t>(), ctr_after.data_ptr<int64_t>());
-  check_launch("rng_draws_debug_kernel");
-  return {vals, below, ctr_after};
-}
-
-// the word -> value halves of the same recipes at given words
-__global__ void __launch_bounds__(64)
-rng_maps_debug_kernel(const int64_t* words, const int64_t* n_below, int64_t B,
-                      double lambd, double mu, double sigma, double* vals,
-                      int64_t* below) {
-  int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= B) return;
-  uint32_t w[4];
-  for (int k = 0; k < 4; ++k) w[k] = (uint32_t)words[row * 4 + k];
-  double* v = vals + row * RNG_DRAW_COLS;
-  double ua = u01_map(w[0], w[1]), ub = u01_map(w[2], w[3]);
-  v[0] = ua;
-  v[1] = ua;
-  v[2] = ub;
-  v[3] = rexp_map(ua, lambd);
-  v[4] = rnormal_map(ua, ub, mu, sigma);
-  v[5] = rlognormal_map(ua, ub, mu, sigma);
-  v[6] = rpareto_inf_map(ua);
-  below[row] = (int64_t)rbelow_map(w[0], (uint32_t)n_below[row]);
-}
-
-std::vector<torch::Tensor> rng_maps_debug(torch::Tensor words,
-                                          torch::Tensor n_below, double lambd,
-                                          double mu, double sigma) {
-  TORCH_CHECK(words.is_cuda() && n_below.is_cuda() &&
-              words.dtype() == torch::kInt64 &&
-              n_below.dtype() == torch::kInt64);
-  TORCH_CHECK(words.dim() == 2 && words.size(1) == 4 && n_below.dim() == 1 &&
-              n_below.size(0) == words.size(0));
-  words = words.contiguous();
-  n_below = n_below.contiguous();
-  int64_t B = words.size(0);
-  auto vals = torch::empty({B, RNG_DRAW_COLS},
-                           words.options().dtype(torch::kFloat64));
-  auto below = torch::empty({B}, words.options());
-  if (B == 0) return {vals, below};
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(rng_maps_debug_kernel, dim3((unsigned)((B + 63) / 64)),
-                     dim3(64), 0, stream, words.data_ptr<int64_t>(),
-                     n_below.data_ptr<int64_t>(), B, lambd, mu, sigma,
-                     vals.data_ptr<double>(), below.data_ptr<int64_t>());
-  check_launch("rng_maps_debug_kernel");
-  return {vals, below};
-}
-
-__global__ void __launch_bounds__(64)
-models_debug_kernel(const double* pc, const double* lc, const int* n,
-                    const double* f, int64_t B, double* P, double* T) {
-  int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= B) return;
-  P[row] = d_job_power<double>(n[row], f[row], pc + row * 3);
-  T[row] = d_unit_time<double>(n[row], f[row], lc + row * 3);
-}
-
-// (pc, lc) coefficient rows as the model drivers take them: f64[B,3] on the
-// GPU, bounded so that no score can reach the searches' "no candidate" value
-static void check_coeff_rows(const torch::Tensor& pc, const torch::Tensor& lc) {
-  TORCH_CHECK(pc.is_cuda() && lc.is_cuda() && pc.dtype() == torch::kFloat64 &&
-              lc.dtype() == torch::kFloat64);
-  TORCH_CHECK(pc.dim() == 2 && pc.size(1) == 3 && lc.sizes() == pc.sizes());
-  TORCH_CHECK(pc.numel() == 0 ||
-                  ((pc.abs() <= 1e6).all().item<bool>() &&
-                   (lc.abs() <= 1e6).all().item<bool>()),
-              "coefficients must be finite and within +-1e6");
-}
-static void check_freq_ladder(const torch::Tensor& freq) {
-  TORCH_CHECK(freq.is_cuda() && freq.dtype() == torch::kFloat64 &&
-              freq.dim() == 1 && freq.size(0) >= 1 && freq.size(0) <= 4096);
-  TORCH_CHECK((freq.abs() <= 1e3).all().item<bool>(),
-              "frequencies must be finite and within +-1e3");
-}
-
-std::vector<torch::Tensor> models_debug(torch::Tensor pc, torch::Tensor lc,
-                                        torch::Tensor n, torch::Tensor f) {
-  check_coeff_rows(pc, lc);
-  int64_t B = pc.size(0);
-  TORCH_CHECK(n.is_cuda() && f.is_cuda() && n.dtype() == torch::kInt32 &&
-              f.dtype() == torch::kFloat64 && n.dim() == 1 && f.dim() == 1 &&
-              n.size(0) == B && f.size(0) == B);
-  pc = pc.contiguous();
-  lc = lc.contiguous();
-  n = n.contiguous();
-  f = f.contiguous();
-  auto P = torch::empty({B}, f.options());
-  auto T = torch::empty({B}, f.options());
-  if (B == 0) return {P, T};
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(models_debug_kernel, dim3((unsigned)((B + 63) / 64)),
-                     dim3(64), 0, stream, pc.data_ptr<double>(),
-                     lc.data_ptr<double>(), n.data_ptr<int>(),
-                     f.data_ptr<double>(), B, P.data_ptr<double>(),
-                     T.data_ptr<double>());
-  check_launch("models_debug_kernel");
-  return {P, T};
-}
-
-template <class F>
-__global__ void __launch_bounds__(64)
-grid_argmin_debug_kernel(const double* pc, const double* lc,
-                         const double* freq, int n_freq, int n_max,
-                         int objective, const double* ci, const double* price,
-                         bool has_ddl, const double* ddl, int* found, int* n,
-                         double* f, double* T, double* P, double* E) {
-  int64_t row = blockIdx.x;
-  GridPick g = wave_grid_argmin<F>(pc + row * 3, lc + row * 3, freq, n_freq,
-                                   n_max, objective, ci[row], price[row],
-                                   has_ddl, ddl[row]);
-  if (threadIdx.x == 0) {
-    found[row] = g.found ? 1 : 0;
-    n[row] = g.n;
-    f[row] = g.f;
-    T[row] = g.T;
-    P[row] = g.P;
-    E[row] = g.E;
-  }
-}
-
-std::vector<torch::Tensor> grid_argmin_debug(
-    torch::Tensor pc, torch::Tensor lc, torch::Tensor freq, int64_t n_max,
-    int64_t objective, torch::Tensor ci, torch::Tensor price, bool has_ddl,
-    torch::Tensor ddl, bool fp32) {
-  check_coeff_rows(pc, lc);
-  check_freq_ladder(freq);
-  int64_t B = pc.size(0);
-  TORCH_CHECK(n_max >= 1 && n_max <= 4096 && objective >= 0 && objective <= 2);
-  for (const torch::Tensor* t : {&ci, &price, &ddl})
-    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kFloat64 &&
-                t->dim() == 1 && t->size(0) == B);
-  TORCH_CHECK(B == 0 || ((ci.abs() <= 1e3).all().item<bool>() &&
-                         (price.abs() <= 1e3).all().item<bool>()),
-              "ci and price must be finite and within +-1e3");
-  pc = pc.contiguous();
-  lc = lc.contiguous();
-  freq = freq.contiguous();
-  ci = ci.contiguous();
-  price = price.contiguous();
-  ddl = ddl.contiguous();
-  auto i32 = pc.options().dtype(torch::kInt32);
-  auto found = torch::empty({B}, i32);
-  auto n = torch::empty({B}, i32);
-  auto f = torch::empty({B}, pc.options());
-  auto T = torch::empty({B}, pc.options());
-  auto P = torch::empty({B}, pc.options());
-  auto E = torch::empty({B}, pc.options());
-  if (B == 0) return {found, n, f, T, P, E};
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  auto kern = fp32 ? grid_argmin_debug_kernel<float>
-                   : grid_argmin_debug_kernel<double>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), 0, stream,
-                     pc.data_ptr<double>(), lc.data_ptr<double>(),
-                     freq.data_ptr<double>(), (int)freq.size(0), (int)n_max,
-                     (int)objective, ci.data_ptr<double>(),
-                     price.data_ptr<double>(), has_ddl, ddl.data_ptr<double>(),
-                     found.data_ptr<int>(), n.data_ptr<int>(),
-                     f.data_ptr<double>(), T.data_ptr<double>(),
-                     P.data_ptr<double>(), E.data_ptr<double>());
-  check_launch("grid_argmin_debug_kernel");
-  return {found, n, f, T, P, E};
-}
-
-template <class F>
-__global__ void __launch_bounds__(64)
-energy_freq_debug_kernel(const double* pc, const double* lc,
-                         const double* freq, int n_freq, const int* n,
-                         double* f) {
-  int64_t row = blockIdx.x;
-  double best = wave_energy_freq<F>(pc + row * 3, lc + row * 3, freq, n_freq,
-                                    n[row]);
-  if (threadIdx.x == 0) f[row] = best;
-}
-
-torch::Tensor energy_freq_debug(torch::Tensor pc, torch::Tensor lc,
-                                torch::Tensor freq, torch::Tensor n,
-                                bool fp32) {
-  check_coeff_rows(pc, lc);
-  check_freq_ladder(freq);
-  int64_t B = pc.size(0);
-  TORCH_CHECK(n.is_cuda() && n.dtype() == torch::kInt32 && n.dim() == 1 &&
-              n.size(0) == B);
-  TORCH_CHECK(B == 0 || (n.abs() <= 4096).all().item<bool>());
-  pc = pc.contiguous();
-  lc = lc.contiguous();
-  freq = freq.contiguous();
-  n = n.contiguous();
-  auto f = torch::empty({B}, pc.options());
-  if (B == 0) return f;
-  hipStream_t stream = at::hip::getCurrentHIPStream();
-  auto kern = fp32 ? energy_freq_debug_kernel<float>
-                   : energy_freq_debug_kernel<double>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), 0, stream,
-                     pc.data_ptr<double>(), lc.data_ptr<double>(),
-                     freq.data_ptr<double>(), (int)freq.size(0),
-                     n.data_ptr<int>(), f.data_ptr<double>());
-  check_launch("energy_freq_debug_kernel");
-  return f;
-}
+namespace dcg {
 
 // ---------------- host side ----------------
-// EngineDesc pointer <- the tensor of the same name and element type
-#define T_PTR(name, type) S_.name = t_[#name].data_ptr<type>()
-// ... for the fields whose pointer type is a same-width alias of the tensor's
-// element type (int64 -> long long / uint64, int8 -> char, f64 rows -> records)
-#define T_ALIAS(name, type) \
-  S_.name = reinterpret_cast<decltype(S_.name)>(t_[#name].data_ptr<type>())
-
 class BatchedSimHip {
  public:
   BatchedSimHip(py::dict tensors, py::dict cfg) {
@@ -2788,40 +2140,9 @@ class BatchedSimHip {
     S_.cl_cap = cfg["cl_cap"].cast<int>();
     S_.jl_cap = cfg["jl_cap"].cast<int>();
 
-    T_PTR(freq_levels, double); T_PTR(pc, double); T_PTR(lc, double);
-    T_PTR(wan_lat, double); T_PTR(wan_bw, double); T_PTR(carbon, double);
-    T_PTR(price24, double); T_PTR(total_gpus, int); T_PTR(p_idle, double);
-    T_PTR(p_sleep, double); T_PTR(p_peak, double); T_PTR(pow_alpha, double);
-    T_PTR(power_gating, int); T_PTR(default_freq, double);
-    T_PTR(slot_off, int); T_PTR(slot_dc, int);
-    T_PTR(now, double); T_PTR(next_log, double); T_ALIAS(rng_ctr, int64_t);
-    T_PTR(jid_ctr, int); T_PTR(done, int); T_PTR(err, int);
-    T_PTR(arr_next, double);
-    T_PTR(busy, int); T_PTR(cur_freq, double); T_PTR(energy_j, double);
-    T_PTR(util_time, double); T_PTR(util_begin, double); T_PTR(acc_unit, double);
-    T_PTR(p_active, double); T_PTR(sum_tpt, double); T_PTR(n_running, int);
-    T_PTR(dc_min_finish, double); T_PTR(dc_min_slot, int);
-    T_PTR(s_finish, double); T_PTR(seq_ctr, int);
-    T_ALIAS(s_rec, double); T_PTR(s_gpus, int16_t); T_ALIAS(s_jtype, int8_t);
-    T_PTR(x_time, double); T_ALIAS(x_rec, double);
-    T_PTR(q_head, int); T_PTR(q_len, int); T_PTR(q_pay, double);
-    if (S_.algo == A_CAP_GREEDY) T_PTR(snap_f, double);
-    T_PTR(q_netlat, float); T_PTR(q_jid, int); T_ALIAS(q_ing, int8_t);
-    T_PTR(b_n, int); T_PTR(b_s, double); T_ALIAS(b_t, int64_t);
-    T_ALIAS(ev_count, int64_t); T_ALIAS(jobs_done, int64_t);
-    T_ALIAS(jobs_done_inf, int64_t);
-    T_PTR(sum_lat, double); T_PTR(sum_lat_inf, double); T_PTR(sum_wait, double);
-    T_PTR(cl_count, int); T_PTR(cl_rows, double);
-    T_PTR(jl_count, int); T_PTR(jl_rows, double);
-
     // arrival-trace replay mode
     S_.trace_mode = opt("trace_mode", 0);
     S_.trace_cap = opt("trace_cap", 0);
-    if (S_.trace_mode) {
-      T_PTR(trace_time, double); T_PTR(trace_size, double);
-      T_ALIAS(trace_dc, int8_t); T_PTR(trace_pos, int);
-    }
-
     // CHSAC-AF extras
     S_.obs_dim = opt("obs_dim", 0);
     S_.sla_p99_ms = opt("sla_p99_ms", 500.0);
@@ -2833,37 +2154,184 @@ class BatchedSimHip {
     S_.n_g = S_.max_gpj;
     S_.rl_det = opt("rl_det", 0);
     S_.tr_limit = opt("tr_limit", 0);
-    if (S_.serve_device) {
-      if (S_.hid > RL_MAX_HID || S_.obs_dim > RL_MAX_OBS ||
-          S_.n_dc > 8 || S_.n_g > 8)
-        throw std::runtime_error("serve_device limits: hid<=256, obs<=64, "
-                                 "n_dc<=8, n_g<=8");
-      S_.pw = t_["policy_weights"].data_ptr<float>();
-    }
     if (S_.algo == A_CHSAC) {
-      T_PTR(req_flag, int); T_PTR(req_obs, float); T_PTR(req_mdc, int);
-      T_PTR(req_mg, int); T_PTR(resp_dc, int); T_PTR(resp_g, int);
-      T_PTR(pend_kind, int); T_PTR(pend_size, double); T_PTR(pend_netlat, float);
-      T_PTR(pend_jid, int); T_PTR(pend_ing, int); T_PTR(pend_jt, int);
-      T_PTR(pend_dc, int); T_PTR(pend_from_inf, int); T_PTR(pend_enq, double);
-      T_PTR(slot_s0, float); T_PTR(x_s0, float);
-      T_PTR(pp_count, int); T_PTR(pp_cursor, int);
-      T_PTR(pp_size, double); T_PTR(pp_done, double); T_PTR(pp_start, double);
-      T_PTR(pp_netlat, float); T_PTR(pp_jid, int); T_PTR(pp_s0, float);
-      T_PTR(pp_ing, uint8_t); T_PTR(pp_dc, uint8_t); T_PTR(pp_pcount, uint8_t);
-      T_PTR(pp_adc, uint8_t); T_PTR(pp_ag, uint8_t); T_PTR(pp_nrew, uint8_t);
-      T_PTR(pp_has_rl, uint8_t);
-      T_PTR(lat_hist, int); T_ALIAS(lat_count, int64_t); T_PTR(lat_sum, double);
       S_.exact_p99 = opt("exact_p99", 0);
       S_.p99_win = opt("p99_win", 2048);
-      if (S_.exact_p99) {
-        T_PTR(p99_sorted, double); T_PTR(p99_ring, double);
-      }
-      T_PTR(tr_count, int); T_PTR(tr_s0, float); T_PTR(tr_s1, float);
-      T_PTR(tr_r, float); T_PTR(tr_costs, float);
-      T_PTR(tr_adc, uint8_t); T_PTR(tr_ag, uint8_t);
-      T_PTR(tr_mdc, uint8_t); T_PTR(tr_mg, uint8_t);
     }
+    // population time series (off unless the host allocated its buffers)
+    ps_.every = opt("pop_series_every", 0);
+
+    check_engine_limits(S_);
+    shmem_bytes();  // an oversized scenario fails here, not at the first launch
+
+    // The contract: every pointer this configuration's kernel may dereference,
+    // with the extent the kernel indexes it to (in elements of the field).
+    const int64_t R = S_.n_rep, D = S_.n_dc, I = S_.n_ing, NS = S_.n_streams,
+                  F = S_.n_freq, TS = S_.total_slots, TC = S_.tcap,
+                  Q = S_.qcap, O = S_.obs_dim;
+    Binder bind(t_);
+    // scenario constants
+    bind(S_.freq_levels, "freq_levels", F);
+    bind(S_.pc, "pc", D * 6);
+    bind(S_.lc, "lc", D * 6);
+    bind(S_.wan_lat, "wan_lat", I * D);
+    bind(S_.wan_bw, "wan_bw", I * D);
+    bind(S_.carbon, "carbon", D);
+    bind(S_.price24, "price24", 24);
+    bind(S_.total_gpus, "total_gpus", D);
+    bind(S_.p_idle, "p_idle", D);
+    bind(S_.p_sleep, "p_sleep", D);
+    bind(S_.p_peak, "p_peak", D);
+    bind(S_.pow_alpha, "pow_alpha", D);
+    bind(S_.power_gating, "power_gating", D);
+    bind(S_.default_freq, "default_freq", D);
+    bind(S_.slot_off, "slot_off", D + 1);
+    bind(S_.slot_dc, "slot_dc", TS);
+    // per-replica scalars
+    bind(S_.now, "now", R);
+    bind(S_.next_log, "next_log", R);
+    bind(S_.rng_ctr, "rng_ctr", R);
+    bind(S_.jid_ctr, "jid_ctr", R);
+    bind(S_.done, "done", R);
+    bind(S_.err, "err", R);
+    bind(S_.arr_next, "arr_next", R * NS);
+    // per (r, dc)
+    bind(S_.busy, "busy", R * D);
+    bind(S_.cur_freq, "cur_freq", R * D);
+    bind(S_.energy_j, "energy_j", R * D);
+    bind(S_.util_time, "util_time", R * D);
+    bind(S_.util_begin, "util_begin", R * D);
+    bind(S_.acc_unit, "acc_unit", R * D);
+    bind(S_.p_active, "p_active", R * D);
+    bind(S_.sum_tpt, "sum_tpt", R * D);
+    bind(S_.n_running, "n_running", R * D);
+    bind(S_.dc_min_finish, "dc_min_finish", R * D);
+    bind(S_.dc_min_slot, "dc_min_slot", R * D);
+    // job slots, transfers, queues
+    bind(S_.s_finish, "s_finish", R * TS);
+    bind(S_.seq_ctr, "seq_ctr", R);
+    bind(S_.s_rec, "s_rec", R * TS);
+    bind(S_.s_gpus, "s_gpus", R * TS);
+    bind(S_.s_jtype, "s_jtype", R * TS);
+    bind(S_.x_time, "x_time", R * TC);
+    bind(S_.x_rec, "x_rec", R * TC);
+    bind(S_.q_head, "q_head", R * D * 2);
+    bind(S_.q_len, "q_len", R * D * 2);
+    bind(S_.q_pay, "q_pay", R * D * 2 * Q * 2);
+    bind(S_.q_netlat, "q_netlat", D * 2 * Q);
+    bind(S_.q_jid, "q_jid", D * 2 * Q);
+    bind(S_.q_ing, "q_ing", D * 2 * Q);
+    // only the cap_greedy / bandit kernels touch these; elsewhere the host
+    // passes placeholders, which are neither bound nor checked
+    if (S_.algo == A_CAP_GREEDY) bind(S_.snap_f, "snap_f", R * TS);
+    else bind.unused("snap_f");
+    if (S_.algo == A_BANDIT) {
+      bind(S_.b_n, "b_n", R * D * 2 * F);
+      bind(S_.b_s, "b_s", R * D * 2 * F);
+    } else {
+      bind.unused("b_n");
+      bind.unused("b_s");
+    }
+    bind(S_.b_t, "b_t", R);
+    // metrics
+    bind(S_.ev_count, "ev_count", R);
+    bind(S_.jobs_done, "jobs_done", R);
+    bind(S_.jobs_done_inf, "jobs_done_inf", R);
+    bind(S_.sum_lat, "sum_lat", R);
+    bind(S_.sum_lat_inf, "sum_lat_inf", R);
+    bind(S_.sum_wait, "sum_wait", R);
+    // logging
+    bind(S_.cl_count, "cl_count", 1);
+    bind(S_.cl_rows, "cl_rows", (int64_t)S_.cl_cap * 15);
+    bind(S_.jl_count, "jl_count", 1);
+    bind(S_.jl_rows, "jl_rows", (int64_t)S_.jl_cap * 11);
+    if (S_.trace_mode) {
+      bind(S_.trace_time, "trace_time", R * NS * S_.trace_cap);
+      bind(S_.trace_size, "trace_size", R * NS * S_.trace_cap);
+      bind(S_.trace_dc, "trace_dc", R * NS * S_.trace_cap);
+      bind(S_.trace_pos, "trace_pos", R * NS);
+    }
+    if (S_.serve_device) {
+      // the seven layers of EngineDesc::pw
+      const int64_t H = S_.hid, G = S_.n_g;
+      bind(S_.pw, "policy_weights",
+           (O * H + H) + 2 * (H * H + H) + (H * H + H) + (H * D + D) +
+               (H * H + H) + (H * G + G));
+    }
+    if (S_.algo == A_CHSAC) {
+      const int64_t PP = S_.pp_cap, TR = S_.tr_cap;
+      bind(S_.req_flag, "req_flag", R);
+      bind(S_.req_obs, "req_obs", R * O);
+      bind(S_.req_mdc, "req_mdc", R);
+      bind(S_.req_mg, "req_mg", R);
+      bind(S_.resp_dc, "resp_dc", R);
+      bind(S_.resp_g, "resp_g", R);
+      bind(S_.pend_kind, "pend_kind", R);
+      bind(S_.pend_size, "pend_size", R);
+      bind(S_.pend_netlat, "pend_netlat", R);
+      bind(S_.pend_jid, "pend_jid", R);
+      bind(S_.pend_ing, "pend_ing", R);
+      bind(S_.pend_jt, "pend_jt", R);
+      bind(S_.pend_dc, "pend_dc", R);
+      bind(S_.pend_from_inf, "pend_from_inf", R);
+      bind(S_.pend_enq, "pend_enq", R);
+      bind(S_.slot_s0, "slot_s0", R * TS * O);
+      bind(S_.x_s0, "x_s0", R * TC * O);
+      bind(S_.pp_count, "pp_count", R);
+      bind(S_.pp_cursor, "pp_cursor", R);
+      bind(S_.pp_size, "pp_size", R * PP);
+      bind(S_.pp_done, "pp_done", R * PP);
+      bind(S_.pp_start, "pp_start", R * PP);
+      bind(S_.pp_netlat, "pp_netlat", R * PP);
+      bind(S_.pp_jid, "pp_jid", R * PP);
+      bind(S_.pp_s0, "pp_s0", R * PP * O);
+      bind(S_.pp_ing, "pp_ing", R * PP);
+      bind(S_.pp_dc, "pp_dc", R * PP);
+      bind(S_.pp_pcount, "pp_pcount", R * PP);
+      bind(S_.pp_adc, "pp_adc", R * PP);
+      bind(S_.pp_ag, "pp_ag", R * PP);
+      bind(S_.pp_nrew, "pp_nrew", R * PP);
+      bind(S_.pp_has_rl, "pp_has_rl", R * PP);
+      bind(S_.lat_hist, "lat_hist", R * 2 * LAT_BINS);
+      bind(S_.lat_count, "lat_count", R * 2);
+      bind(S_.lat_sum, "lat_sum", R * 2);
+      if (S_.exact_p99) {
+        bind(S_.p99_sorted, "p99_sorted", R * 2 * S_.p99_win);
+        bind(S_.p99_ring, "p99_ring", R * 2 * S_.p99_win);
+      } else {
+        bind.unused("p99_sorted");
+        bind.unused("p99_ring");
+      }
+      bind(S_.tr_count, "tr_count", 1);
+      bind(S_.tr_s0, "tr_s0", TR * O);
+      bind(S_.tr_s1, "tr_s1", TR * O);
+      bind(S_.tr_r, "tr_r", TR);
+      bind(S_.tr_costs, "tr_costs", TR * 3);
+      bind(S_.tr_adc, "tr_adc", TR);
+      bind(S_.tr_ag, "tr_ag", TR);
+      bind(S_.tr_mdc, "tr_mdc", TR);
+      bind(S_.tr_mg, "tr_mg", TR);
+    }
+
+    if (ps_.every > 0) {
+      auto smp = t_.find("ps_samples");
+      TORCH_CHECK(smp != t_.end() && smp->second.dim() == 4 &&
+                      smp->second.size(1) == S_.n_dc + 1 &&
+                      smp->second.size(2) == PS_K &&
+                      smp->second.size(3) == S_.n_rep,
+                  "ps_samples must be [t_cap][n_dc+1][", PS_K, "][n_rep]");
+      ps_.t_cap = (int)smp->second.size(0);
+      TORCH_CHECK(t_.count("ps_time") && t_.count("ps_tick") &&
+                      t_["ps_time"].numel() == ps_.t_cap &&
+                      t_["ps_tick"].numel() == S_.n_rep,
+                  "ps_time must be [t_cap], ps_tick [n_rep]");
+      bind(ps_.samples, "ps_samples", (int64_t)ps_.t_cap * (D + 1) * PS_K * R);
+      bind(ps_.time, "ps_time", ps_.t_cap);
+      bind(ps_.tick, "ps_tick", R);
+    }
+    contract_ = bind.rows();
+    on_gpu_ = bind.on_gpu();
+    device_ = bind.device_str();
 
     // DCG_ADVANCE_PASSES: unset or 0 = plan automatically, 1 = always a
     // single launch, k = at most k passes
@@ -2871,24 +2339,11 @@ class BatchedSimHip {
       int k = std::atoi(ev);
       if (k > 0) max_passes_ = k;
     }
-
-    // population time series (off unless the host allocated its buffers)
-    ps_.every = opt("pop_series_every", 0);
-    if (ps_.every > 0) {
-      auto& smp = t_["ps_samples"];
-      TORCH_CHECK(smp.dim() == 4 && smp.size(1) == S_.n_dc + 1 &&
-                      smp.size(2) == PS_K && smp.size(3) == S_.n_rep &&
-                      smp.is_contiguous(),
-                  "ps_samples must be [t_cap][n_dc+1][", PS_K, "][n_rep]");
-      ps_.t_cap = (int)smp.size(0);
-      TORCH_CHECK(t_["ps_time"].numel() == ps_.t_cap &&
-                      t_["ps_tick"].numel() == S_.n_rep,
-                  "ps_time must be [t_cap], ps_tick [n_rep]");
-      ps_.samples = smp.data_ptr<double>();
-      ps_.time = t_["ps_time"].data_ptr<double>();
-      ps_.tick = t_["ps_tick"].data_ptr<int>();
-    }
   }
+
+  // the tensors this engine bound, in bind order: (field, dtype, required
+  // numel); a field its kernel never dereferences has numel -1
+  const std::vector<Binder::Row>& contract() const { return contract_; }
 
   // Create a CU-masked stream for the advance kernel, excluding the LAST
   // `n_reserved` CUs.  The advance kernel's blocks are persistent for a
@@ -2901,6 +2356,7 @@ class BatchedSimHip {
   // tried and did not help — see NEGATIVE RESULT above; the uncapped full
   // grid measured ~20% more events/s.)
   void enable_masked_stream(int n_reserved) {
+    require_gpu("enable_masked_stream");
     if (masked_stream_) return;
     hipDeviceProp_t prop;
     int dev;
@@ -2950,6 +2406,7 @@ class BatchedSimHip {
   // dynamic-LDS size, times CUs, times replicas per block.  Kernel and LDS
   // size are fixed for the engine's lifetime, so one query serves it.
   int resident_capacity() {
+    require_gpu("resident_capacity");
     if (forced_capacity_ > 0) return forced_capacity_;
     if (queried_capacity_ == 0) {
       int per_cu = 0, dev = 0, n_cu = 0;
@@ -2994,6 +2451,7 @@ class BatchedSimHip {
 
   // enqueue one advance chunk; returns immediately (stream-async)
   void advance(double t_target, int64_t max_ev) {
+    require_gpu("advance");
     const int rpb = REPLICAS_PER_BLOCK;
     const LaunchPlan plan = plan_for(max_ev);
     AdvanceFn fn = kernel(plan.windows.size() > 1);
@@ -3008,6 +2466,14 @@ class BatchedSimHip {
   }
 
  private:
+  // The constructor binds tensors on any device without a HIP call, so the
+  // contract can be checked on CPU tensors; nothing is launched on them.
+  void require_gpu(const char* what) const {
+    if (!on_gpu_)
+      throw std::runtime_error(std::string(what) + ": the engine's tensors "
+                               "are on " + device_ + ", not on a GPU");
+  }
+
   // the advance kernel's stream: the CU-masked one once enabled
   hipStream_t stream() const {
     return masked_stream_ ? masked_stream_
@@ -3047,8 +2513,10 @@ class BatchedSimHip {
                              S_.algo == A_CHSAC).stride();
     if (shmem > 64 * 1024)
       throw std::runtime_error(
-          "scenario too large for the LDS-mirrored engine (total_slots + "
-          "tcap exceed the 64 KiB dynamic-LDS budget per block)");
+          "scenario too large for the LDS-mirrored engine (total_slots = " +
+          std::to_string(S_.total_slots) + " + tcap = " +
+          std::to_string(S_.tcap) + " need " + std::to_string(shmem) +
+          " B, above the 64 KiB dynamic-LDS budget per block)");
     return shmem;
   }
 
@@ -3061,11 +2529,11 @@ class BatchedSimHip {
   long long min_quantum_ = PLAN_MIN_QUANTUM;
   long long launch_cost_ = PLAN_LAUNCH_COST;
   std::unordered_map<std::string, torch::Tensor> t_;
+  std::vector<Binder::Row> contract_;
+  bool on_gpu_ = false;           // the bound tensors' device is a GPU
+  std::string device_;            // ... and its name, for messages
   hipStream_t masked_stream_ = nullptr;
 };
-
-#undef T_PTR
-#undef T_ALIAS
 
 }  // namespace dcg
 
@@ -3085,6 +2553,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("launch_plan", &dcg::BatchedSimHip::launch_plan,
            "windows (first, count, split, ev_a, ev_b) advance() would launch",
            py::arg("max_events"))
+      .def("contract", &dcg::BatchedSimHip::contract,
+           "bound tensors in bind order: (field, dtype, required numel; -1 = "
+           "never dereferenced in this configuration)")
       .def("resident_capacity", &dcg::BatchedSimHip::resident_capacity)
       .def("enable_masked_stream", &dcg::BatchedSimHip::enable_masked_stream,
            py::arg("n_reserved_cus"))
@@ -3101,47 +2572,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",
         py::arg("pw"), py::arg("obs"), py::arg("hid"), py::arg("n_dc"),
         py::arg("n_g"));
-  m.def("rl_forward_debug", &dcg::rl_forward_debug,
-        "batched actor forward via the in-kernel serving math "
-        "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",
-        py::arg("pw"), py::arg("obs"), py::arg("hid"), py::arg("n_dc"),
-        py::arg("n_g"));
-  m.def("wave_reduce_debug", &dcg::wave_reduce_debug,
-        "production wave_argmin_f64 / wave_argmin_idx_f64 over each row of "
-        "(vals[B,64] f64, idx[B,64] i32) -> (value, lane, value, index)",
-        py::arg("vals"), py::arg("idx"));
-  m.def("first_empty_debug", &dcg::first_empty_debug,
-        "production first-empty-slot search over each row of rows[B,L] f64 "
-        "-> lowest k with rows[k] >= 1e300, INT_MAX if none",
-        py::arg("rows"));
-  m.def("philox_debug", &dcg::philox_debug,
-        "production philox4x32 per row of (keys[B] i64, ctrs[B] i64) -> "
-        "words[B,4] i64",
-        py::arg("keys"), py::arg("ctrs"));
-  m.def("rng_draws_debug", &dcg::rng_draws_debug,
-        "every production draw from a fresh state at (keys[B], ctrs[B]) -> "
-        "(vals[B,7] f64 = u01, u01x2 a, u01x2 b, rexp, rnormal, rlognormal, "
-        "rpareto_inf; rbelow[B] i64; ctr_after[B,7] i64 = u01, u01x2, rexp, "
-        "rbelow, rnormal, rlognormal, rpareto_inf)",
-        py::arg("keys"), py::arg("ctrs"), py::arg("n_below"),
-        py::arg("lambd"), py::arg("mu"), py::arg("sigma"));
-  m.def("rng_maps_debug", &dcg::rng_maps_debug,
-        "the word -> value halves of the draws at words[B,4] i64 -> "
-        "(vals[B,7] f64 as rng_draws_debug, rbelow[B] i64)",
-        py::arg("words"), py::arg("n_below"), py::arg("lambd"),
-        py::arg("mu"), py::arg("sigma"));
-  m.def("models_debug", &dcg::models_debug,
-        "production d_job_power<double> / d_unit_time<double> per row of "
-        "(pc[B,3], lc[B,3], n[B] i32, f[B]) -> (P, T)",
-        py::arg("pc"), py::arg("lc"), py::arg("n"), py::arg("f"));
-  m.def("grid_argmin_debug", &dcg::grid_argmin_debug,
-        "production wave_grid_argmin, one 64-thread block per row -> "
-        "(found i32, n i32, f, T, P, E)",
-        py::arg("pc"), py::arg("lc"), py::arg("freq"), py::arg("n_max"),
-        py::arg("objective"), py::arg("ci"), py::arg("price"),
-        py::arg("has_ddl"), py::arg("ddl"), py::arg("fp32"));
-  m.def("energy_freq_debug", &dcg::energy_freq_debug,
-        "production wave_energy_freq, one 64-thread block per row -> f[B]",
-        py::arg("pc"), py::arg("lc"), py::arg("freq"), py::arg("n"),
-        py::arg("fp32"));
+  dcg::bind_debug_entries(m);
 }

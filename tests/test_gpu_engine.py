@@ -971,3 +971,21 @@ def test_chsac_host_serving_uses_mfma_forward():
     assert st["jobs_completed"] > 0
     assert eng.rl_updates > 0
     assert int(eng.t["err"].max().item()) == 0
+
+
+@needs_gpu
+def test_short_tensor_is_rejected_before_any_launch():
+    """The extension's constructor checks every tensor's extent against what
+    the kernel indexes: a state tensor one element short is a ValueError that
+    names the field, raised before anything is launched."""
+    from distributed_cluster_gpus_amd.engine.state import engine_cfg
+    eng = make_engine(replicas=4, duration=20.0)
+    cfg = engine_cfg(eng.dims, eng.sc, eng.arrival_inf, eng.arrival_trn)
+    eng._mod.BatchedSimHip(eng.t, cfg)          # the engine's own state binds
+    for field in ("q_pay", "s_rec", "busy"):
+        bad = dict(eng.t)
+        bad[field] = eng.t[field].reshape(-1)[:-1].clone()
+        assert bad[field].is_cuda
+        with pytest.raises(ValueError, match=f"'{field}': required"):
+            eng._mod.BatchedSimHip(bad, cfg)
+    assert int(eng.t["ev_count"].sum().item()) == 0   # nothing ran
