@@ -35,8 +35,8 @@ from ..ops import load_sim_hip
 from ..utils.csvlog import ClusterLogWriter, JobLogWriter
 from ..utils.timers import ThroughputMeter
 from .oracle import ALGOS
-from .state import (INF, RL_HID, SERIES_METRICS, alloc_state, engine_cfg,
-                    engine_dims, load_tensors)
+from .state import (ARR_CAP, INF, RL_HID, SERIES_METRICS, alloc_state,
+                    engine_cfg, engine_dims, load_tensors)
 
 # the fleet row of the population series (per-DC rows: SERIES_METRICS)
 SERIES_FLEET = "ALL"
@@ -69,6 +69,7 @@ class BatchedEngine:
                  tr_cap: int = 262144, arrival_trace=None,
                  subwave: int = 64,
                  pop_series: bool = False, pop_series_every: int = 1,
+                 arrival_pregen: bool = True, arr_cap: int = ARR_CAP,
                  **_unused):
         if algo not in ALGOS:
             raise ValueError(f"unknown algo {algo!r}")
@@ -186,7 +187,12 @@ class BatchedEngine:
             elastic_scaling=elastic_scaling, rl_exact_p99=rl_exact_p99,
             serve_device=self._serve_device, weights_buffer=self._mfma_serve,
             rl_deterministic=rl_deterministic, rl_tr_limit=rl_tr_limit,
-            rl_train_interval=rl_train_interval)
+            rl_train_interval=rl_train_interval,
+            # arrivals pre-generated lane-parallel into a per-replica ring
+            # (ops/csrc/hip/arrival_ring.hpp); the 8-lane build draws inline
+            # and stays the independent reference
+            arrival_pregen=bool(arrival_pregen) and subwave == 64,
+            arr_cap=arr_cap)
         self.dims = dims
         if self.pop_series:
             ps_bytes = dims.ps_cap * (n_dc + 1) * len(SERIES_METRICS) * R * 8

@@ -13,6 +13,12 @@ dereferences the field: ``snap_f`` is (1, 1) unless the algo is cap_greedy,
 ``b_n`` / ``b_s`` have a leading dim of 1 unless it is bandit, ``p99_sorted``
 / ``p99_ring`` are (1, 1, 1) without exact_p99.  The extension neither binds
 nor checks those (``contract()`` lists them as not required).
+
+The arrival ring (``arr_ring``, ``arr_head``, ``arr_count``, the generator's
+frontier ``gen_arr_next`` / ``gen_ctr`` and the ``arr_more`` flag;
+ops/csrc/hip/arrival_ring.hpp) exists only where arrivals are pre-generated:
+every algo but chsac_af, outside trace mode, unless ``arrival_pregen=False``.
+It is ordinary state: a checkpoint saves and restores it with the rest.
 """
 import math
 from dataclasses import dataclass
@@ -35,6 +41,8 @@ SERIES_METRICS = ("freq", "busy", "running", "q_inf", "q_trn", "power_w",
                   "energy_j")
 RL_HID = 256       # served actor's hidden width (RL_MAX_HID)
 P99_WIN = 2048     # exact-p99 sliding window (the reference's 2048 sojourns)
+ARR_CAP = 4096     # arrival-ring records per replica (32 B each): one
+                   # advance() call of up to this many events is one sub-step
 
 
 @dataclass(frozen=True)
@@ -76,6 +84,7 @@ class EngineDims:
     weights_numel: int          # flat actor-weights buffer; 1 = placeholder
     rl_det: int
     tr_limit: int
+    arr_cap: int = 0            # arrival ring: records per replica; 0 = off
 
     @property
     def is_rl(self) -> bool:
@@ -107,11 +116,15 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
                 rl_exact_p99: bool = False, serve_device: bool = False,
                 weights_buffer: bool = False, rl_deterministic: bool = False,
                 rl_tr_limit: Optional[int] = None,
-                rl_train_interval: int = 256) -> EngineDims:
+                rl_train_interval: int = 256,
+                arrival_pregen: bool = True,
+                arr_cap: int = ARR_CAP) -> EngineDims:
     """``n_rep`` is this rank's replica count; ``serve_device`` /
     ``weights_buffer`` say whether the kernel serves the policy itself and
     whether the flat actor-weights buffer is needed at all (it also feeds the
-    host path's matrix-core forward)."""
+    host path's matrix-core forward).  ``arrival_pregen`` asks for the arrival
+    ring of ``arr_cap`` records (a power of two) per replica; chsac_af and
+    trace mode never have one."""
     is_rl = algo == "chsac_af"
     n_dc = scenario.n_dc
     end_time, log_interval = float(duration), float(log_interval)
@@ -128,6 +141,9 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
     # to bound policy staleness to one cycle of transitions
     tr_limit = int(rl_tr_limit) if rl_tr_limit is not None else \
         min(tr_cap // 2, int(rl_train_interval) * 256)
+    pregen = bool(arrival_pregen) and not is_rl and arrival_trace is None
+    if pregen and (int(arr_cap) < 1 or int(arr_cap) & (int(arr_cap) - 1)):
+        raise ValueError(f"arr_cap must be a power of two, got {arr_cap}")
     return EngineDims(
         algo=algo, n_rep=int(n_rep), n_dc=n_dc, n_ing=scenario.n_ing,
         n_freq=scenario.n_freq,
@@ -157,7 +173,8 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
         weights_numel=policy_weights_numel(obs_dim, n_dc, n_g)
         if (is_rl and (serve_device or weights_buffer)) else 1,
         rl_det=int(bool(rl_deterministic) and is_rl),
-        tr_limit=tr_limit if is_rl else 0)
+        tr_limit=tr_limit if is_rl else 0,
+        arr_cap=int(arr_cap) if pregen else 0)
 
 
 def alloc_state(dims: EngineDims, scenario: Scenario, device,
@@ -278,6 +295,18 @@ def alloc_state(dims: EngineDims, scenario: Scenario, device,
             (d.ps_cap, n_dc + 1, len(SERIES_METRICS), R), **f64)
         t["ps_time"] = torch.zeros(d.ps_cap, **f64)
         t["ps_tick"] = torch.zeros(R, **i32)
+
+    # arrival ring: records (ARec, 32 B) the generator appends and the
+    # advance kernel consumes, and the generator's frontier.  The frontier is
+    # re-read from arr_next / rng_ctr whenever the ring is empty, so it needs
+    # no seeding here.
+    if d.arr_cap:
+        t["arr_ring"] = torch.zeros((R, d.arr_cap, 4), **f64)
+        t["arr_head"] = torch.zeros(R, **i32)
+        t["arr_count"] = torch.zeros(R, **i32)
+        t["gen_arr_next"] = torch.full((R, NS), INF, **f64)
+        t["gen_ctr"] = torch.zeros(R, **i64)
+        t["arr_more"] = torch.zeros(1, **i32)
 
     # arrival-trace replay mode (exact single-replica parity testing):
     # arrivals come from a recorded (time, size) FIFO per stream
@@ -409,4 +438,5 @@ def engine_cfg(dims: EngineDims, scenario: Scenario, arrival_inf,
         "serve_device": d.serve_device, "rl_hid": RL_HID, "rl_det": d.rl_det,
         "tr_limit": d.tr_limit, "exact_p99": d.exact_p99,
         "p99_win": P99_WIN, "pop_series_every": d.ps_every,
+        "arr_cap": d.arr_cap,
     }

@@ -38,6 +38,7 @@ DCG_ELEM(long long, kInt64);
 DCG_ELEM(uint64_t, kInt64);
 DCG_ELEM(SRec, kFloat64);
 DCG_ELEM(XRec, kFloat64);
+DCG_ELEM(ARec, kFloat64);
 #undef DCG_ELEM
 
 class Binder {

@@ -38,6 +38,15 @@ struct SRec {            // 64 B: cold job-slot payload
 };
 static_assert(sizeof(SRec) == 64, "SRec must be one 64B record");
 
+struct ARec {            // 32 B: one pre-generated arrival (arrival ring)
+  double size;           // job size
+  double t_next;         // the stream's next arrival time (arr_next[stream])
+  uint64_t ctr;          // the replica's Philox counter after this arrival
+  int stream;            // ing * 2 + jtype
+  int dc;                // routed DC (rbelow); -1 where the kernel routes
+};
+static_assert(sizeof(ARec) == 32, "ARec must be one 32B record");
+
 enum Algo { A_DEFAULT = 0, A_CAP_UNIFORM, A_CAP_GREEDY, A_JOINT_NF, A_BANDIT,
             A_CARBON_COST, A_ECO_ROUTE, A_DEBUG, A_CHSAC };
 
@@ -50,7 +59,10 @@ enum ReqFlag : int { REQ_IDLE = 0, REQ_PENDING = 1, REQ_READY = 2 };
 constexpr int LAT_BINS = 64;  // log10 bins over sojourn [1e-4 s, 1e4 s)
 
 enum Err : int { ERR_NONE = 0, ERR_QUEUE_OVF = 1, ERR_XFER_OVF = 2,
-                 ERR_SLOT_OVF = 4, ERR_LOG_OVF = 8 };
+                 ERR_SLOT_OVF = 4, ERR_LOG_OVF = 8,
+                 // an arrival found the ring empty, or its head record is for
+                 // another stream (must never fire)
+                 ERR_ARR_RING = 16 };
 
 // compile-time limits of the advance kernel's LDS-resident state and of
 // the in-kernel actor forward (checked by engine_limits.hpp)
@@ -252,9 +264,29 @@ struct EngineDesc {
   unsigned char* tr_mg;           // [cap]
 };
 
+// The arrival ring (arrival_ring.hpp): arrivals pre-generated by
+// pregen_arrivals_kernel, consumed in order by the PRE advance kernels.  A
+// trailing kernel argument of its own, as PopSeriesDesc is, so that EngineDesc
+// and with it the PRE = false kernels stay what they were.  cap == 0: off
+// (chsac, trace mode, the 8-lane build).
+struct ArrRing {
+  int cap;                        // records per replica, a power of two
+  ARec* ring;                     // [r][cap]
+  int* head;                      // [r] slot of the next record to consume
+  int* count;                     // [r] records generated, not yet consumed
+  // the generator's frontier: stream times and counter after the LAST
+  // GENERATED record (arr_next / rng_ctr: after the last CONSUMED one)
+  double* gen_arr_next;           // [r][n_streams]
+  uint64_t* gen_ctr;              // [r]
+  int* more;                      // [1] set by a replica that used up its
+                                  //   event budget: a later sub-step of the
+                                  //   same call may still have work
+};
+
 // the Python side allocates the records as float64 rows (s_rec [.., 8],
-// x_rec [.., 4]); the binder casts those rows to the record types
+// x_rec and arr_ring [.., 4]); the binder casts those rows to the record types
 static_assert(sizeof(SRec) == 8 * sizeof(double), "s_rec rows are 8 f64 wide");
 static_assert(sizeof(XRec) == 4 * sizeof(double), "x_rec rows are 4 f64 wide");
+static_assert(sizeof(ARec) == 4 * sizeof(double), "arr_ring rows are 4 f64 wide");
 
 }  // namespace dcg

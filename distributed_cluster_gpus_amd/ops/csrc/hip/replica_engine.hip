@@ -38,6 +38,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "arrival_ring.hpp"
 #include "engine_bind.hpp"
 #include "engine_desc.hpp"
 #include "engine_limits.hpp"
@@ -465,8 +466,7 @@ __device__ double draw_interarrival(Ctx& c, int jt, double t) {
     if (max_rate > 0) {
       for (int it = 0; it < 4096; ++it) {
         double w = rexp(c.rng, max_rate);
-        double lam = fmax(0.0, rate * (1.0 + amp *
-            sin(2.0 * M_PI * fmod(t + w, period) / period)));
+        double lam = thinning_rate(rate, amp, period, t, w);
         if (u01(c.rng) <= lam / max_rate) { ia = w; break; }
       }
     }
@@ -1324,10 +1324,12 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
 #else
 #define DCG_ADVANCE_BOUNDS __launch_bounds__(THREADS_PER_BLOCK)
 #endif
-template <int ALGO, bool PS, bool WIN>
+// PRE: arrivals come from the arrival ring (arrival_ring.hpp) instead of
+// being drawn here; the PRE = false kernels are the ones from before the ring
+template <int ALGO, bool PS, bool WIN, bool PRE = false>
 __global__ void DCG_ADVANCE_BOUNDS
 advance_kernel(EngineDesc S, double t_target, long long max_ev,
-               PopSeriesDesc P, LaunchWindow W) {
+               PopSeriesDesc P, LaunchWindow W, ArrRing A) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
   // (64-lane build: the slot, and with it the replica index and the event
@@ -1338,6 +1340,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
   // chsac always gets the whole ensemble in one launch (its launch cadence
   // carries meaning)
   static_assert(!(WIN && ALGO == A_CHSAC), "chsac has no windowed kernel");
+  static_assert(!(PRE && (ALGO == A_CHSAC || SUBW != 64)),
+                "chsac draws at its arrivals; the 8-lane build has no ring");
   if (slot_id >= (WIN ? W.count : S.n_rep)) return;
   // windowed: the event counter runs up to max_ev = W.ev_a for every slot, a
   // scalar bound in both builds; slots past the split start it at the
@@ -1372,6 +1376,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
   }
   c.rng.key = S.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(S.rep_id_offset + c.r));
   c.rng.ctr = S.rng_ctr[c.r];
+  // the replica's part of the arrival ring: next slot, records left
+  int ring_head = 0, ring_left = 0;
+  if (PRE) {
+    ring_head = sub_uniform_i32(A.head[c.r]);
+    ring_left = sub_uniform_i32(A.count[c.r]);
+  }
 
   const int NS = S.n_streams;
   int64_t sbase = (int64_t)c.r * S.total_slots;
@@ -1596,7 +1606,21 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
       if (lane == 0) c.hs->jid_ctr = jid;
       double size;
       int trace_d = -1;
-      if (S.trace_mode) {
+      if (PRE) {
+        // this arrival's size, random route, the stream's next time and the
+        // counter after its draws, as pregen_arrivals_kernel recorded them
+        ARec rec = A.ring[(int64_t)c.r * A.cap + ring_head];
+        if (ring_left <= 0 || sub_uniform_i32(rec.stream) != idx) {
+          if (lane == 0) atomicOr(&S.err[c.r], ERR_ARR_RING);
+        }
+        size = rec.size;
+        trace_d = sub_uniform_i32(rec.dc);
+        c.rng.ctr = (uint64_t)sub_uniform_i64((long long)rec.ctr);
+        ring_head = ring_slot(ring_head, 1, A.cap);
+        --ring_left;
+        if (lane == 0) c.hs->arr_next[idx] = rec.t_next;
+        lds_fence();
+      } else if (S.trace_mode) {
         // replay mode: this arrival's size, routed DC and the stream's next
         // time come from the recorded trace
         int64_t tb = ((int64_t)c.r * S.n_streams + idx) * S.trace_cap;
@@ -1636,7 +1660,7 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
       } else {
       // routing
       int d_sel;
-      if (S.trace_mode && trace_d >= 0) {
+      if ((PRE || S.trace_mode) && trace_d >= 0) {
         d_sel = trace_d;
       } else if (ALGO == A_ECO_ROUTE) {
         double price = S.eco_obj == 2 ? c.price_kwh(t_min) : 0.0;
@@ -1704,10 +1728,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
       d_sel = sub_uniform_i32(d_sel);
       push_transfer(c, t_min, jt, ing, size, jid, d_sel);
       // next arrival for this stream; in replay mode it was already set
+      if (!PRE) {
       double ia = D_INF;
       if (!S.trace_mode) ia = draw_interarrival(c, jt, t_min);
       if (lane == 0 && !S.trace_mode) c.hs->arr_next[idx] = t_min + ia;
       lds_fence();
+      }
       }  // end non-chsac arrival path
 
     } else if (kind == 1) {
@@ -1917,6 +1943,11 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
     S.next_log[c.r] = c.hs->next_log;
     S.now[c.r] = c.now;
     S.rng_ctr[c.r] = c.rng.ctr;
+    if (PRE) {
+      A.head[c.r] = ring_head;
+      A.count[c.r] = max(ring_left, 0);
+      if (n_events >= max_ev) *A.more = 1;
+    }
     S.ev_count[c.r] += n_events - ev_skip;
     S.sum_lat[c.r] = c.hs->sum_lat;
     S.sum_lat_inf[c.r] = c.hs->sum_lat_inf;
@@ -2143,6 +2174,18 @@ class BatchedSimHip {
     // arrival-trace replay mode
     S_.trace_mode = opt("trace_mode", 0);
     S_.trace_cap = opt("trace_cap", 0);
+    // arrival ring (0 = arrivals drawn inside the advance kernel)
+    ar_.cap = opt("arr_cap", 0);
+    if (ar_.cap != 0) {
+      if (!arr_cap_valid(ar_.cap))
+        throw std::invalid_argument(
+            "engine limits: arr_cap = " + std::to_string(ar_.cap) +
+            ", required a power of two");
+      if (S_.algo == A_CHSAC || S_.trace_mode)
+        throw std::invalid_argument(
+            "arr_cap = " + std::to_string(ar_.cap) + ": chsac_af and "
+            "trace mode have no pre-generated arrivals, required arr_cap = 0");
+    }
     // CHSAC-AF extras
     S_.obs_dim = opt("obs_dim", 0);
     S_.sla_p99_ms = opt("sla_p99_ms", 500.0);
@@ -2250,6 +2293,22 @@ class BatchedSimHip {
       bind(S_.trace_size, "trace_size", R * NS * S_.trace_cap);
       bind(S_.trace_dc, "trace_dc", R * NS * S_.trace_cap);
       bind(S_.trace_pos, "trace_pos", R * NS);
+    }
+    if (ar_.cap > 0) {
+#if DCG_SUBWAVE == 64
+      bind(ar_.ring, "arr_ring", R * ar_.cap);
+      bind(ar_.head, "arr_head", R);
+      bind(ar_.count, "arr_count", R);
+      bind(ar_.gen_arr_next, "gen_arr_next", R * NS);
+      bind(ar_.gen_ctr, "gen_ctr", R);
+      bind(ar_.more, "arr_more", 1);
+#else
+      // the 8-lane build draws inline: it stays the independent reference
+      for (const char* n : {"arr_ring", "arr_head", "arr_count",
+                            "gen_arr_next", "gen_ctr", "arr_more"})
+        bind.unused(n);
+      ar_.cap = 0;
+#endif
     }
     if (S_.serve_device) {
       // the seven layers of EngineDesc::pw
@@ -2427,6 +2486,16 @@ class BatchedSimHip {
     return queried_capacity_;
   }
 
+  // Sub-steps of advance(., max_ev): with the arrival ring, consecutive
+  // budgets of at most arr_cap events (arrival_plan.hpp), each topped up and
+  // planned on its own; without it, the whole call.
+  std::vector<long long> substeps(long long max_ev) const {
+    std::vector<long long> out;
+    const int n = ar_.cap > 0 ? substep_count(max_ev, ar_.cap) : 1;
+    for (int i = 0; i < n; ++i) out.push_back(substep_budget(max_ev, n, i));
+    return out;
+  }
+
   // The launches advance(., max_ev) issues.  One launch of everything for
   // chsac (its launch cadence carries meaning: tr_limit, pending requests)
   // and on the CU-masked stream (its capacity is not the device's).
@@ -2443,9 +2512,10 @@ class BatchedSimHip {
   std::vector<std::tuple<int, int, int, int64_t, int64_t>> launch_plan(
       int64_t max_ev) {
     std::vector<std::tuple<int, int, int, int64_t, int64_t>> out;
-    for (const LaunchWindow& w : plan_for(max_ev).windows)
-      out.emplace_back(w.first, w.count, w.split, (int64_t)w.ev_a,
-                       (int64_t)w.ev_b);
+    for (long long ev : substeps(max_ev))
+      for (const LaunchWindow& w : plan_for(ev).windows)
+        out.emplace_back(w.first, w.count, w.split, (int64_t)w.ev_a,
+                         (int64_t)w.ev_b);
     return out;
   }
 
@@ -2453,17 +2523,59 @@ class BatchedSimHip {
   void advance(double t_target, int64_t max_ev) {
     require_gpu("advance");
     const int rpb = REPLICAS_PER_BLOCK;
-    const LaunchPlan plan = plan_for(max_ev);
-    AdvanceFn fn = kernel(plan.windows.size() > 1);
     size_t shmem = shmem_bytes();
     dim3 block(THREADS_PER_BLOCK);
-    for (const LaunchWindow& w : plan.windows) {
-      dim3 grid((w.count + rpb - 1) / rpb);
-      hipLaunchKernelGGL(fn, grid, block, shmem, stream(), S_, t_target,
-                         w.ev_a, ps_, w);
-      check_launch("advance_kernel launch failed");
+    const std::vector<long long> subs = substeps(max_ev);
+    for (size_t i = 0; i < subs.size(); ++i) {
+      const long long ev = subs[i];
+      // A call of many sub-steps (a budget far above what t_target allows)
+      // asks the device every SUBSTEP_CHECK of them whether any replica
+      // still ran into its event budget; if none did, every later sub-step
+      // would find all replicas at t_target or done and change nothing.
+      if (subs.size() > SUBSTEP_CHECK && i % SUBSTEP_CHECK == 0) {
+        if (i > 0 && !budget_limited()) break;
+        hipError_t e = hipMemsetAsync(ar_.more, 0, sizeof(int), stream());
+        if (e != hipSuccess)
+          throw std::runtime_error(std::string("advance: ") +
+                                   hipGetErrorString(e));
+      }
+#if DCG_SUBWAVE == 64
+      if (ar_.cap > 0) {
+        // same stream, so the ring is topped up before the windows read it
+        const int per_block = PG_THREADS / PG_GROUP;
+        hipLaunchKernelGGL(pregen_arrivals_kernel,
+                           dim3((S_.n_rep + per_block - 1) / per_block),
+                           dim3(PG_THREADS), 0, stream(), S_, ar_, t_target,
+                           ev);
+        check_launch("pregen_arrivals_kernel launch failed");
+      }
+#endif
+      const LaunchPlan plan = plan_for(ev);
+      AdvanceFn fn = kernel(plan.windows.size() > 1);
+      for (const LaunchWindow& w : plan.windows) {
+        dim3 grid((w.count + rpb - 1) / rpb);
+        hipLaunchKernelGGL(fn, grid, block, shmem, stream(), S_, t_target,
+                           w.ev_a, ps_, w, ar_);
+        check_launch("advance_kernel launch failed");
+      }
     }
   }
+
+  // did any replica use up its event budget since arr_more was cleared
+  // (waits for the stream)
+  bool budget_limited() {
+    int more = 1;
+    hipError_t e = hipMemcpyAsync(&more, ar_.more, sizeof(int),
+                                  hipMemcpyDeviceToHost, stream());
+    if (e == hipSuccess) e = hipStreamSynchronize(stream());
+    if (e != hipSuccess)
+      throw std::runtime_error(std::string("advance: ") +
+                               hipGetErrorString(e));
+    return more != 0;
+  }
+
+  // arrivals come from the ring (false: drawn inside the advance kernel)
+  bool arrival_pregen() const { return ar_.cap > 0; }
 
  private:
   // The constructor binds tensors on any device without a HIP call, so the
@@ -2481,27 +2593,46 @@ class BatchedSimHip {
   }
 
   using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc,
-                             LaunchWindow);
+                             LaunchWindow, ArrRing);
 
   // this engine's instantiation: one per Algo, in enum order, without and
   // with the population-series sampling, without and with the window
-  // arithmetic (chsac: never windowed)
+  // arithmetic (chsac: never windowed), without and with the arrival ring
+  // (64-lane build only; chsac: never)
   AdvanceFn kernel(bool windowed) const {
-#define DCG_ADVANCE_ROW(PS, WIN, CHSAC)                                        \
-  {advance_kernel<A_DEFAULT, PS, WIN>,    advance_kernel<A_CAP_UNIFORM, PS, WIN>, \
-   advance_kernel<A_CAP_GREEDY, PS, WIN>, advance_kernel<A_JOINT_NF, PS, WIN>, \
-   advance_kernel<A_BANDIT, PS, WIN>,     advance_kernel<A_CARBON_COST, PS, WIN>, \
-   advance_kernel<A_ECO_ROUTE, PS, WIN>,  advance_kernel<A_DEBUG, PS, WIN>,    \
+#define DCG_ADVANCE_ROW(PS, WIN, PRE, CHSAC)                                   \
+  {advance_kernel<A_DEFAULT, PS, WIN, PRE>,                                    \
+   advance_kernel<A_CAP_UNIFORM, PS, WIN, PRE>,                                \
+   advance_kernel<A_CAP_GREEDY, PS, WIN, PRE>,                                 \
+   advance_kernel<A_JOINT_NF, PS, WIN, PRE>,                                   \
+   advance_kernel<A_BANDIT, PS, WIN, PRE>,                                     \
+   advance_kernel<A_CARBON_COST, PS, WIN, PRE>,                                \
+   advance_kernel<A_ECO_ROUTE, PS, WIN, PRE>,                                  \
+   advance_kernel<A_DEBUG, PS, WIN, PRE>,                                      \
    CHSAC}
+#define DCG_ADVANCE_TABLE(PRE)                                                 \
+  {{DCG_ADVANCE_ROW(false, false, PRE, nullptr),                               \
+    DCG_ADVANCE_ROW(true, false, PRE, nullptr)},                               \
+   {DCG_ADVANCE_ROW(false, true, PRE, nullptr),                                \
+    DCG_ADVANCE_ROW(true, true, PRE, nullptr)}}
     static const AdvanceFn kernels[2][2][A_CHSAC + 1] = {
-        {DCG_ADVANCE_ROW(false, false, (advance_kernel<A_CHSAC, false, false>)),
-         DCG_ADVANCE_ROW(true, false, (advance_kernel<A_CHSAC, true, false>))},
-        {DCG_ADVANCE_ROW(false, true, nullptr),
-         DCG_ADVANCE_ROW(true, true, nullptr)}};
-#undef DCG_ADVANCE_ROW
+        {DCG_ADVANCE_ROW(false, false, false,
+                         (advance_kernel<A_CHSAC, false, false>)),
+         DCG_ADVANCE_ROW(true, false, false,
+                         (advance_kernel<A_CHSAC, true, false>))},
+        {DCG_ADVANCE_ROW(false, true, false, nullptr),
+         DCG_ADVANCE_ROW(true, true, false, nullptr)}};
     if (S_.algo < 0 || S_.algo > A_CHSAC)
       throw std::runtime_error("unsupported algo for HIP engine");
     AdvanceFn fn = kernels[windowed][ps_.samples != nullptr][S_.algo];
+#if DCG_SUBWAVE == 64
+    static const AdvanceFn pre_kernels[2][2][A_CHSAC + 1] =
+        DCG_ADVANCE_TABLE(true);
+    if (ar_.cap > 0)
+      fn = pre_kernels[windowed][ps_.samples != nullptr][S_.algo];
+#endif
+#undef DCG_ADVANCE_TABLE
+#undef DCG_ADVANCE_ROW
     if (!fn) throw std::runtime_error("chsac has no windowed advance kernel");
     return fn;
   }
@@ -2520,8 +2651,10 @@ class BatchedSimHip {
     return shmem;
   }
 
+  static constexpr size_t SUBSTEP_CHECK = 8;
   EngineDesc S_{};
   PopSeriesDesc ps_{};            // samples == nullptr: feature off
+  ArrRing ar_{};                  // cap == 0: arrivals drawn in the kernel
   // launch plan (launch_plan.hpp)
   int forced_capacity_ = 0;       // 0: the runtime's occupancy answer
   int queried_capacity_ = 0;      // cache of that answer
@@ -2557,6 +2690,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "bound tensors in bind order: (field, dtype, required numel; -1 = "
            "never dereferenced in this configuration)")
       .def("resident_capacity", &dcg::BatchedSimHip::resident_capacity)
+      .def("arrival_pregen", &dcg::BatchedSimHip::arrival_pregen,
+           "arrivals come from the pre-generated ring (false: drawn inside "
+           "the advance kernel)")
       .def("enable_masked_stream", &dcg::BatchedSimHip::enable_masked_stream,
            py::arg("n_reserved_cus"))
       .def("masked_active", &dcg::BatchedSimHip::masked_active)
