@@ -33,3 +33,22 @@ class ThroughputMeter:
     @property
     def per_sec(self) -> float:
         return self.count / self.elapsed_s
+
+
+class Lap:
+    """One running phase: ``stop()`` (or leaving the ``with`` block) adds the
+    wall time since construction to ``totals[key]``.  Phases that overlap
+    without nesting keep a named lap each and stop it where the phase ends."""
+
+    def __init__(self, totals: dict, key: str):
+        self.totals, self.key = totals, key
+        self.t0 = time.perf_counter()
+
+    def stop(self):
+        self.totals[self.key] += time.perf_counter() - self.t0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.stop()
