@@ -147,12 +147,9 @@ def _pad_ticks(s: SeriesStats, T: int) -> SeriesStats:
         s.metrics, s.dc_names)
 
 
-def _merge_pair(a: SeriesStats, b: SeriesStats) -> SeriesStats:
-    """Chan et al. parallel combination of (n, mean, M2) per cell; an empty
-    side contributes nothing (its NaN mean never enters the arithmetic)."""
-    assert a.metrics == b.metrics and a.dc_names == b.dc_names
-    T = max(len(a.time), len(b.time))
-    a, b = _pad_ticks(a, T), _pad_ticks(b, T)
+def _chan(a, b):
+    """(mean, m2) of the union of two groups with fields n / mean / m2 of
+    equal shape, per cell."""
     na, nb = a.n.astype(np.float64), b.n.astype(np.float64)
     n = na + nb
     ea, eb = a.n == 0, b.n == 0
@@ -163,6 +160,16 @@ def _merge_pair(a: SeriesStats, b: SeriesStats) -> SeriesStats:
     m2 = a.m2 + b.m2 + delta * delta * (na * nb / safe_n)
     mean = np.where(ea, b.mean, np.where(eb, a.mean, mean))
     m2 = np.where(ea, b.m2, np.where(eb, a.m2, m2))
+    return mean, m2
+
+
+def _merge_pair(a: SeriesStats, b: SeriesStats) -> SeriesStats:
+    """Chan et al. parallel combination of (n, mean, M2) per cell; an empty
+    side contributes nothing (its NaN mean never enters the arithmetic)."""
+    assert a.metrics == b.metrics and a.dc_names == b.dc_names
+    T = max(len(a.time), len(b.time))
+    a, b = _pad_ticks(a, T), _pad_ticks(b, T)
+    mean, m2 = _chan(a, b)
     # a tick's time comes from whichever side has reached it
     a_has = (a.n.reshape(T, -1).max(axis=1) > 0) if a.n.size \
         else np.zeros(T, bool)
@@ -178,8 +185,12 @@ def merge_series_stats(parts: Sequence[SeriesStats]) -> SeriesStats:
     parts = list(parts)
     if not parts:
         raise ValueError("merge_series_stats needs at least one SeriesStats")
+    return _tree_merge(parts, _merge_pair)
+
+
+def _tree_merge(parts: list, pair):
     while len(parts) > 1:
-        nxt = [_merge_pair(parts[i], parts[i + 1])
+        nxt = [pair(parts[i], parts[i + 1])
                for i in range(0, len(parts) - 1, 2)]
         if len(parts) % 2:
             nxt.append(parts[-1])
@@ -238,4 +249,214 @@ def population_series_report(engine, out_dir: str,
     emit(q, out_dir, "population_series_queue_len", kind="line", x="time_s",
          y="queue_len_mean", hue="dc",
          title="Queue length per DC, mean over replicas", ylabel="jobs")
+    return df
+
+
+# ---------------------------------------------------------------------------
+# Latency distribution: per-replica histograms of the job sojourn
+# (BatchedEngine(latency_hist=True); reduced on the GPU by ops latency_reduce)
+# ---------------------------------------------------------------------------
+# The bins of ops/csrc/hip/lat_bins.hpp, restated in numpy: exponent and top 3
+# mantissa bits of the f64 pattern, 8 bins per octave from 2^-14 s to 2^18 s.
+LH_BINS = 256
+_LH_SHIFT = 49
+_LH_KEY0 = (1023 - 14) << 3
+JOB_TYPES = ["inference", "training"]
+DEFAULT_QUANTILES = (0.5, 0.9, 0.99, 0.999)
+
+
+def latency_bin_edges():
+    """(lower[256], upper[256]) in seconds.  Bin b holds lower <= x < upper;
+    bin 0 also everything below, bin 255 everything above (upper = +inf)."""
+    keys = (np.arange(LH_BINS + 1, dtype=np.uint64) + np.uint64(_LH_KEY0)) \
+        << np.uint64(_LH_SHIFT)
+    edges = keys.view(np.float64).copy()
+    upper = edges[1:].copy()
+    upper[-1] = np.inf
+    return edges[:-1], upper
+
+
+def latency_bins(latencies) -> np.ndarray:
+    """Bin index of each sojourn (seconds); negatives and NaN count as 0."""
+    x = np.ascontiguousarray(latencies, dtype=np.float64)
+    x = np.where(x > 0.0, x, 0.0)
+    key = (x.view(np.uint64) >> np.uint64(_LH_SHIFT)).astype(np.int64)
+    return np.clip(key - _LH_KEY0, 0, LH_BINS - 1)
+
+
+def latency_histogram(latencies) -> np.ndarray:
+    """int64[256] histogram of sojourns in the engine's bins, so that the
+    ``latency_s`` column of a scalar engine's job_log.csv yields the same
+    report as the batched engine's in-kernel histograms."""
+    return np.bincount(latency_bins(latencies).reshape(-1),
+                       minlength=LH_BINS).astype(np.int64)
+
+
+def latency_quantile(pop_hist, q: float) -> np.ndarray:
+    """Quantile q of histograms [..., 256]: the upper edge of the first bin
+    whose cumulative count reaches ceil(q * n); NaN where n == 0.  The true
+    order statistic x of that rank satisfies x < reported <= 1.125 * x
+    whenever 2^-14 <= x < 1.875 * 2^17 seconds."""
+    h = np.asarray(pop_hist, dtype=np.int64)
+    cum = np.cumsum(h, axis=-1)
+    n = cum[..., -1]
+    rank = np.ceil(q * n.astype(np.float64)).astype(np.int64)
+    b = (cum < rank[..., None]).sum(axis=-1)
+    upper = latency_bin_edges()[1]
+    return np.where(n > 0, upper[np.minimum(b, LH_BINS - 1)], np.nan)
+
+
+def quantile_label(q: float) -> str:
+    return f"p{q * 100:.6g}"
+
+
+@dataclass
+class LatencyStats:
+    """Latency distribution over the replica ensemble.  ``pop_hist`` is
+    [len(dc_names), 2, 256] int64, the histogram pooled over the replicas;
+    ``n``, ``mean``, ``m2``, ``min`` and ``max`` are [len(dc_names), 2,
+    len(metrics)]: statistics of each per-replica figure over the replicas
+    that have one (a replica with no finished job in a cell has no quantile
+    and no SLA-miss fraction there).  ``metrics`` is one label per quantile,
+    then ``sla_miss_frac`` and ``jobs``.  The last entry of ``dc_names`` is
+    the fleet row."""
+    pop_hist: np.ndarray
+    n: np.ndarray
+    mean: np.ndarray
+    m2: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    quantiles: List[float]
+    metrics: List[str]
+    dc_names: List[str]
+    job_types: List[str]
+    bin_lo: np.ndarray
+    bin_hi: np.ndarray
+    sla_s: float
+
+    @classmethod
+    def from_tensor(cls, pop_hist, stats, quantiles, dc_names,
+                    sla_s) -> "LatencyStats":
+        """pop_hist: [n_row, 2, 256], stats: [n_row, 2, Q + 2, 5] = {n, mean,
+        M2, min, max} (tensors or arrays, on the host)."""
+        a = np.asarray(stats, dtype=np.float64)
+        lo, hi = latency_bin_edges()
+        qs = [float(q) for q in quantiles]
+        return cls(pop_hist=np.asarray(pop_hist).astype(np.int64),
+                   n=a[..., 0].astype(np.int64), mean=a[..., 1].copy(),
+                   m2=a[..., 2].copy(), min=a[..., 3].copy(),
+                   max=a[..., 4].copy(), quantiles=qs,
+                   metrics=[quantile_label(q) for q in qs] +
+                   ["sla_miss_frac", "jobs"],
+                   dc_names=list(dc_names), job_types=list(JOB_TYPES),
+                   bin_lo=lo, bin_hi=hi, sla_s=float(sla_s))
+
+    def to_array(self) -> np.ndarray:
+        """[n_row, 2, K, 5] float64 = {n, mean, M2, min, max}."""
+        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
+                         self.min, self.max], axis=-1)
+
+    def to_flat(self) -> np.ndarray:
+        """Histogram and statistics as one f64 vector, the form that travels
+        between ranks; counts are exact below 2^53."""
+        return np.concatenate([self.pop_hist.astype(np.float64).reshape(-1),
+                               self.to_array().reshape(-1)])
+
+    @classmethod
+    def from_flat(cls, flat, quantiles, dc_names, sla_s) -> "LatencyStats":
+        """Inverse of to_flat."""
+        flat = np.asarray(flat, dtype=np.float64)
+        n_row, K = len(dc_names), len(quantiles) + 2
+        n_pop = n_row * 2 * LH_BINS
+        return cls.from_tensor(
+            flat[:n_pop].astype(np.int64).reshape(n_row, 2, LH_BINS),
+            flat[n_pop:].reshape(n_row, 2, K, 5), quantiles, dc_names, sla_s)
+
+    def pooled_quantile(self, q: float) -> np.ndarray:
+        """[n_row, 2]: quantile q of the pooled histogram."""
+        return latency_quantile(self.pop_hist, q)
+
+
+def _merge_latency_pair(a: LatencyStats, b: LatencyStats) -> LatencyStats:
+    assert a.quantiles == b.quantiles and a.dc_names == b.dc_names \
+        and a.sla_s == b.sla_s
+    mean, m2 = _chan(a, b)
+    return LatencyStats(a.pop_hist + b.pop_hist, a.n + b.n, mean, m2,
+                        np.fmin(a.min, b.min), np.fmax(a.max, b.max),
+                        a.quantiles, a.metrics, a.dc_names, a.job_types,
+                        a.bin_lo, a.bin_hi, a.sla_s)
+
+
+def merge_latency_stats(parts: Sequence[LatencyStats]) -> LatencyStats:
+    """Combine disjoint replica groups (shards, ranks, separate runs):
+    histograms add; n / mean / M2 merge by the Chan formula of
+    merge_series_stats in the same tree order, min and max directly."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_latency_stats needs at least one LatencyStats")
+    return _tree_merge(parts, _merge_latency_pair)
+
+
+LATENCY_COLUMNS = ["dc", "type", "metric", "n", "mean", "std", "stderr",
+                   "ci_lo", "ci_hi", "min", "max"]
+LATENCY_HIST_COLUMNS = ["dc", "type", "bin_lo_s", "bin_hi_s", "count"]
+
+
+def latency_frame(stats: LatencyStats, confidence: float = 0.95) -> pd.DataFrame:
+    """Long-form rows (DC, then job type, then metric) with the sample
+    standard deviation (ddof=1), the standard error of the mean and the
+    normal-approximation confidence interval over the replicas; zero width
+    when n < 2."""
+    z = _z(confidence)
+    D, J, K = len(stats.dc_names), len(stats.job_types), len(stats.metrics)
+    n = stats.n.reshape(-1)
+    mean = stats.mean.reshape(-1)
+    multi = n > 1
+    std = np.where(multi, np.sqrt(np.maximum(stats.m2.reshape(-1), 0.0)
+                                  / np.where(multi, n - 1, 1)), 0.0)
+    se = np.where(multi, std / np.sqrt(np.where(multi, n, 1)), 0.0)
+    return pd.DataFrame({
+        "dc": np.repeat(np.asarray(stats.dc_names, object), J * K),
+        "type": np.tile(np.repeat(np.asarray(stats.job_types, object), K), D),
+        "metric": np.tile(np.asarray(stats.metrics, object), D * J),
+        "n": n, "mean": mean, "std": std, "stderr": se,
+        "ci_lo": mean - z * se, "ci_hi": mean + z * se,
+        "min": stats.min.reshape(-1), "max": stats.max.reshape(-1),
+    }, columns=LATENCY_COLUMNS)
+
+
+def latency_hist_frame(stats: LatencyStats) -> pd.DataFrame:
+    """The pooled histogram, one row per non-empty (DC, job type, bin)."""
+    d, j, b = np.nonzero(stats.pop_hist)
+    return pd.DataFrame({
+        "dc": np.asarray(stats.dc_names, object)[d],
+        "type": np.asarray(stats.job_types, object)[j],
+        "bin_lo_s": stats.bin_lo[b], "bin_hi_s": stats.bin_hi[b],
+        "count": stats.pop_hist[d, j, b],
+    }, columns=LATENCY_HIST_COLUMNS)
+
+
+def latency_report(engine, out_dir: str, quantiles=DEFAULT_QUANTILES,
+                   confidence: float = 0.95, logger=None) -> pd.DataFrame:
+    """Write latency_quantiles.csv and latency_hist.csv (schema:
+    docs/log_format.md) and log, per job type, the fleet's pooled p99 against
+    the SLA.  Returns the long-form quantile frame."""
+    import logging
+    import os
+
+    from ..utils.logging import LOGGER_NAME
+    stats = engine.latency_distribution(quantiles)
+    df = latency_frame(stats, confidence)
+    os.makedirs(out_dir, exist_ok=True)
+    df.to_csv(os.path.join(out_dir, "latency_quantiles.csv"), index=False)
+    latency_hist_frame(stats).to_csv(
+        os.path.join(out_dir, "latency_hist.csv"), index=False)
+    log = logger or logging.getLogger(LOGGER_NAME)
+    p99 = stats.pooled_quantile(0.99)[-1]
+    jobs = stats.pop_hist[-1].sum(axis=-1)
+    for j, name in enumerate(stats.job_types):
+        verdict = "no jobs" if jobs[j] == 0 else \
+            ("within" if p99[j] <= stats.sla_s else "MISSES")
+        log.info(f"latency_hist: {name} pooled p99 <= {p99[j]:.4g} s over "
+                 f"{int(jobs[j])} jobs, SLA {stats.sla_s:g} s: {verdict}")
     return df

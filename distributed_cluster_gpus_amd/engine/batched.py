@@ -39,8 +39,8 @@ from ..utils.csvlog import ClusterLogWriter, JobLogWriter
 from ..utils.logging import LOGGER_NAME
 from ..utils.timers import Lap, ThroughputMeter
 from .oracle import ALGOS
-from .state import (ARR_CAP, INF, RL_HID, SERIES_METRICS, alloc_state,
-                    engine_cfg, engine_dims, load_tensors)
+from .state import (ARR_CAP, INF, LH_BINS, RL_HID, SERIES_METRICS,
+                    alloc_state, engine_cfg, engine_dims, load_tensors)
 
 # the fleet row of the population series (per-DC rows: SERIES_METRICS)
 SERIES_FLEET = "ALL"
@@ -101,6 +101,8 @@ class BatchedEngine:
                  subwave: int = 64,
                  pop_series: bool = False, pop_series_every: int = 1,
                  arrival_pregen: bool = True, arr_cap: int = ARR_CAP,
+                 latency_hist: bool = False,
+                 latency_sla_s: Optional[float] = None,
                  **_unused):
         if algo not in ALGOS:
             raise ValueError(f"unknown algo {algo!r}")
@@ -177,8 +179,15 @@ class BatchedEngine:
             # (ops/csrc/hip/arrival_ring.hpp); the 8-lane build draws inline
             # and stays the independent reference
             arrival_pregen=bool(arrival_pregen) and subwave == 64,
-            arr_cap=arr_cap)
+            arr_cap=arr_cap, latency_hist=latency_hist,
+            latency_sla_s=latency_sla_s)
         self.dims = dims
+        if dims.lat_hist:
+            lh_bytes = R * n_dc * 2 * (LH_BINS + 1) * 4
+            (logger or logging.getLogger(LOGGER_NAME)).info(
+                f"latency_hist: {R} replicas x {n_dc} DCs x 2 types x "
+                f"({LH_BINS} bins + 1) x 4 B = {lh_bytes} bytes "
+                f"({lh_bytes / 2**20:.1f} MiB), SLA {dims.lat_sla_s:g} s")
         if self.pop_series:
             ps_bytes = dims.ps_cap * (n_dc + 1) * len(SERIES_METRICS) * R * 8
             (logger or logging.getLogger(LOGGER_NAME)).info(
@@ -396,6 +405,42 @@ class BatchedEngine:
         parts = [p.cpu() for p in allgather_series_stats(flat)]
         return merge_series_stats(
             [wrap(p[:-T], p[-T:]) for p in parts]).trimmed()
+
+    # ---------------- latency histograms ----------------
+    def latency_hist(self):
+        """Raw device views of the per-replica latency histograms: ``hist``
+        [R, n_dc, 2, 256] (bins: analysis/montecarlo.latency_bin_edges),
+        ``over`` [R, n_dc, 2] (finishes with sojourn > ``sla_s``)."""
+        if not self.dims.lat_hist:
+            raise RuntimeError("engine was built without latency_hist=True")
+        return {"hist": self.t["lh_hist"], "over": self.t["lh_over"],
+                "sla_s": self.dims.lat_sla_s}
+
+    def latency_distribution(self, quantiles=(0.5, 0.9, 0.99, 0.999)):
+        """Latency quantiles, SLA-miss fraction and job count per (DC, job
+        type) and fleet-wide as a LatencyStats (analysis/montecarlo.py): the
+        histogram pooled over the replicas, and n / mean / M2 / min / max of
+        every per-replica figure over the replicas that have one.  Valid on an
+        unfinished run.  Under torch.distributed the per-rank results are
+        merged, so every rank holds the global one."""
+        from ..analysis.montecarlo import LatencyStats, merge_latency_stats
+        from ..parallel.dist import allgather_series_stats, is_distributed
+        lh = self.latency_hist()
+        qs = [float(q) for q in quantiles]
+        pop, _, stats = self._mod.latency_reduce(
+            lh["hist"], lh["over"], torch.tensor(qs, dtype=torch.float64))
+        names = list(self.sc.dc_names) + [SERIES_FLEET]
+        n_row, K = len(names), len(qs) + 2
+        mine = LatencyStats.from_tensor(
+            pop.cpu().view(n_row, 2, LH_BINS), stats.cpu().view(n_row, 2, K, 5),
+            quantiles=qs, dc_names=names, sla_s=lh["sla_s"])
+        if not (self.world > 1 and is_distributed()):
+            return mine
+        # the histogram travels as f64 with the statistics: exact below 2^53
+        parts = allgather_series_stats(torch.from_numpy(mine.to_flat()))
+        return merge_latency_stats(
+            [LatencyStats.from_flat(p.cpu().numpy(), qs, names, lh["sla_s"])
+             for p in parts])
 
     # ---------------- state checkpointing (capability extension) ----------
     def save_state(self, path: str):

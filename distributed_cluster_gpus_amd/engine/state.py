@@ -19,6 +19,10 @@ frontier ``gen_arr_next`` / ``gen_ctr`` and the ``arr_more`` flag;
 ops/csrc/hip/arrival_ring.hpp) exists only where arrivals are pre-generated:
 every algo but chsac_af, outside trace mode, unless ``arrival_pregen=False``.
 It is ordinary state: a checkpoint saves and restores it with the rest.
+
+The latency histograms (``lh_hist``, ``lh_over``; ops/csrc/hip/lat_hist.hpp)
+exist only when asked for (``latency_hist=True``); their presence is what
+selects the recording kernels.  Ordinary state as well.
 """
 import math
 from dataclasses import dataclass
@@ -43,6 +47,7 @@ RL_HID = 256       # served actor's hidden width (RL_MAX_HID)
 P99_WIN = 2048     # exact-p99 sliding window (the reference's 2048 sojourns)
 ARR_CAP = 4096     # arrival-ring records per replica (32 B each): one
                    # advance() call of up to this many events is one sub-step
+LH_BINS = 256      # latency-histogram bins (ops/csrc/hip/lat_bins.hpp)
 
 
 @dataclass(frozen=True)
@@ -85,6 +90,8 @@ class EngineDims:
     rl_det: int
     tr_limit: int
     arr_cap: int = 0            # arrival ring: records per replica; 0 = off
+    lat_hist: bool = False      # per-replica latency histograms
+    lat_sla_s: float = 0.5      # ... and the sojourn their SLA-miss count uses
 
     @property
     def is_rl(self) -> bool:
@@ -118,13 +125,16 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
                 rl_tr_limit: Optional[int] = None,
                 rl_train_interval: int = 256,
                 arrival_pregen: bool = True,
-                arr_cap: int = ARR_CAP) -> EngineDims:
+                arr_cap: int = ARR_CAP, latency_hist: bool = False,
+                latency_sla_s: Optional[float] = None) -> EngineDims:
     """``n_rep`` is this rank's replica count; ``serve_device`` /
     ``weights_buffer`` say whether the kernel serves the policy itself and
     whether the flat actor-weights buffer is needed at all (it also feeds the
     host path's matrix-core forward).  ``arrival_pregen`` asks for the arrival
     ring of ``arr_cap`` records (a power of two) per replica; chsac_af and
-    trace mode never have one."""
+    trace mode never have one.  ``latency_hist`` asks for the per-replica
+    latency histograms; ``latency_sla_s`` (default ``sla_p99_ms / 1000``) is
+    the sojourn above which a finish counts as an SLA miss."""
     is_rl = algo == "chsac_af"
     n_dc = scenario.n_dc
     end_time, log_interval = float(duration), float(log_interval)
@@ -174,7 +184,10 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
         if (is_rl and (serve_device or weights_buffer)) else 1,
         rl_det=int(bool(rl_deterministic) and is_rl),
         tr_limit=tr_limit if is_rl else 0,
-        arr_cap=int(arr_cap) if pregen else 0)
+        arr_cap=int(arr_cap) if pregen else 0,
+        lat_hist=bool(latency_hist),
+        lat_sla_s=float(latency_sla_s) if latency_sla_s is not None
+        else float(sla_p99_ms) / 1000.0)
 
 
 def alloc_state(dims: EngineDims, scenario: Scenario, device,
@@ -308,6 +321,12 @@ def alloc_state(dims: EngineDims, scenario: Scenario, device,
         t["gen_ctr"] = torch.zeros(R, **i64)
         t["arr_more"] = torch.zeros(1, **i32)
 
+    # latency histograms (opt-in): every replica counts each job finish by
+    # (DC, job type, sojourn bin), and the finishes above the SLA
+    if d.lat_hist:
+        t["lh_hist"] = torch.zeros((R, n_dc, 2, LH_BINS), **i32)
+        t["lh_over"] = torch.zeros((R, n_dc, 2), **i32)
+
     # arrival-trace replay mode (exact single-replica parity testing):
     # arrivals come from a recorded (time, size) FIFO per stream
     if d.trace_mode:
@@ -438,5 +457,5 @@ def engine_cfg(dims: EngineDims, scenario: Scenario, arrival_inf,
         "serve_device": d.serve_device, "rl_hid": RL_HID, "rl_det": d.rl_det,
         "tr_limit": d.tr_limit, "exact_p99": d.exact_p99,
         "p99_win": P99_WIN, "pop_series_every": d.ps_every,
-        "arr_cap": d.arr_cap,
+        "arr_cap": d.arr_cap, "lat_sla_s": d.lat_sla_s,
     }

@@ -42,6 +42,7 @@
 #include "engine_bind.hpp"
 #include "engine_desc.hpp"
 #include "engine_limits.hpp"
+#include "lat_hist.hpp"
 #include "launch_plan.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
@@ -1326,10 +1327,13 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
 #endif
 // PRE: arrivals come from the arrival ring (arrival_ring.hpp) instead of
 // being drawn here; the PRE = false kernels are the ones from before the ring
-template <int ALGO, bool PS, bool WIN, bool PRE = false>
+// LAT: every job finish is counted into the replica's latency histogram
+// (lat_hist.hpp); its descriptor L is one more trailing argument, and the
+// LAT = false kernels never look at it
+template <int ALGO, bool PS, bool WIN, bool PRE = false, bool LAT = false>
 __global__ void DCG_ADVANCE_BOUNDS
 advance_kernel(EngineDesc S, double t_target, long long max_ev,
-               PopSeriesDesc P, LaunchWindow W, ArrRing A) {
+               PopSeriesDesc P, LaunchWindow W, ArrRing A, LatHistDesc L) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
   // (64-lane build: the slot, and with it the replica index and the event
@@ -1800,6 +1804,9 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
           c.hs->jobs_done_inf += 1;
           c.hs->sum_lat_inf += t_min - start;
         }
+        // the sojourn of the job row emitted below, counted for every replica
+        if (LAT)
+          lat_hist_record(L, c.r, S.n_dc, d, jt, fmax(0.0, t_min - start));
         if (ALGO == A_BANDIT) {
           // reward = -E_pred (energy per unit at the used f); match the arm
           // by NEAREST ladder frequency (f_used is stored f32, so exact f64
@@ -2203,6 +2210,9 @@ class BatchedSimHip {
     }
     // population time series (off unless the host allocated its buffers)
     ps_.every = opt("pop_series_every", 0);
+    // latency histograms (off unless the host allocated them)
+    const bool lat_on = t_.count("lh_hist") != 0;
+    lh_.sla_s = opt("lat_sla_s", S_.sla_p99_ms / 1000.0);
 
     check_engine_limits(S_);
     shmem_bytes();  // an oversized scenario fails here, not at the first launch
@@ -2388,6 +2398,10 @@ class BatchedSimHip {
       bind(ps_.time, "ps_time", ps_.t_cap);
       bind(ps_.tick, "ps_tick", R);
     }
+    if (lat_on) {
+      bind(lh_.hist, "lh_hist", R * D * 2 * LH_BINS);
+      bind(lh_.over, "lh_over", R * D * 2);
+    }
     contract_ = bind.rows();
     on_gpu_ = bind.on_gpu();
     device_ = bind.device_str();
@@ -2555,7 +2569,7 @@ class BatchedSimHip {
       for (const LaunchWindow& w : plan.windows) {
         dim3 grid((w.count + rpb - 1) / rpb);
         hipLaunchKernelGGL(fn, grid, block, shmem, stream(), S_, t_target,
-                           w.ev_a, ps_, w, ar_);
+                           w.ev_a, ps_, w, ar_, lh_);
         check_launch("advance_kernel launch failed");
       }
     }
@@ -2593,43 +2607,46 @@ class BatchedSimHip {
   }
 
   using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc,
-                             LaunchWindow, ArrRing);
+                             LaunchWindow, ArrRing, LatHistDesc);
 
   // this engine's instantiation: one per Algo, in enum order, without and
   // with the population-series sampling, without and with the window
   // arithmetic (chsac: never windowed), without and with the arrival ring
-  // (64-lane build only; chsac: never)
+  // (64-lane build only; chsac: never), without and with the latency
+  // histograms
   AdvanceFn kernel(bool windowed) const {
-#define DCG_ADVANCE_ROW(PS, WIN, PRE, CHSAC)                                   \
-  {advance_kernel<A_DEFAULT, PS, WIN, PRE>,                                    \
-   advance_kernel<A_CAP_UNIFORM, PS, WIN, PRE>,                                \
-   advance_kernel<A_CAP_GREEDY, PS, WIN, PRE>,                                 \
-   advance_kernel<A_JOINT_NF, PS, WIN, PRE>,                                   \
-   advance_kernel<A_BANDIT, PS, WIN, PRE>,                                     \
-   advance_kernel<A_CARBON_COST, PS, WIN, PRE>,                                \
-   advance_kernel<A_ECO_ROUTE, PS, WIN, PRE>,                                  \
-   advance_kernel<A_DEBUG, PS, WIN, PRE>,                                      \
+#define DCG_ADVANCE_ROW(PS, WIN, PRE, LAT, CHSAC)                              \
+  {advance_kernel<A_DEFAULT, PS, WIN, PRE, LAT>,                               \
+   advance_kernel<A_CAP_UNIFORM, PS, WIN, PRE, LAT>,                           \
+   advance_kernel<A_CAP_GREEDY, PS, WIN, PRE, LAT>,                            \
+   advance_kernel<A_JOINT_NF, PS, WIN, PRE, LAT>,                              \
+   advance_kernel<A_BANDIT, PS, WIN, PRE, LAT>,                                \
+   advance_kernel<A_CARBON_COST, PS, WIN, PRE, LAT>,                           \
+   advance_kernel<A_ECO_ROUTE, PS, WIN, PRE, LAT>,                             \
+   advance_kernel<A_DEBUG, PS, WIN, PRE, LAT>,                                 \
    CHSAC}
-#define DCG_ADVANCE_TABLE(PRE)                                                 \
-  {{DCG_ADVANCE_ROW(false, false, PRE, nullptr),                               \
-    DCG_ADVANCE_ROW(true, false, PRE, nullptr)},                               \
-   {DCG_ADVANCE_ROW(false, true, PRE, nullptr),                                \
-    DCG_ADVANCE_ROW(true, true, PRE, nullptr)}}
-    static const AdvanceFn kernels[2][2][A_CHSAC + 1] = {
-        {DCG_ADVANCE_ROW(false, false, false,
-                         (advance_kernel<A_CHSAC, false, false>)),
-         DCG_ADVANCE_ROW(true, false, false,
-                         (advance_kernel<A_CHSAC, true, false>))},
-        {DCG_ADVANCE_ROW(false, true, false, nullptr),
-         DCG_ADVANCE_ROW(true, true, false, nullptr)}};
+#define DCG_ADVANCE_TABLE(PRE, LAT, CHSAC, CHSAC_PS)                           \
+  {{DCG_ADVANCE_ROW(false, false, PRE, LAT, CHSAC),                            \
+    DCG_ADVANCE_ROW(true, false, PRE, LAT, CHSAC_PS)},                         \
+   {DCG_ADVANCE_ROW(false, true, PRE, LAT, nullptr),                           \
+    DCG_ADVANCE_ROW(true, true, PRE, LAT, nullptr)}}
+    // [LAT][windowed][PS][algo]
+    static const AdvanceFn kernels[2][2][2][A_CHSAC + 1] = {
+        DCG_ADVANCE_TABLE(false, false,
+                          (advance_kernel<A_CHSAC, false, false>),
+                          (advance_kernel<A_CHSAC, true, false>)),
+        DCG_ADVANCE_TABLE(false, true,
+                          (advance_kernel<A_CHSAC, false, false, false, true>),
+                          (advance_kernel<A_CHSAC, true, false, false, true>))};
     if (S_.algo < 0 || S_.algo > A_CHSAC)
       throw std::runtime_error("unsupported algo for HIP engine");
-    AdvanceFn fn = kernels[windowed][ps_.samples != nullptr][S_.algo];
+    const bool lat = lh_.hist != nullptr, ps = ps_.samples != nullptr;
+    AdvanceFn fn = kernels[lat][windowed][ps][S_.algo];
 #if DCG_SUBWAVE == 64
-    static const AdvanceFn pre_kernels[2][2][A_CHSAC + 1] =
-        DCG_ADVANCE_TABLE(true);
-    if (ar_.cap > 0)
-      fn = pre_kernels[windowed][ps_.samples != nullptr][S_.algo];
+    static const AdvanceFn pre_kernels[2][2][2][A_CHSAC + 1] = {
+        DCG_ADVANCE_TABLE(true, false, nullptr, nullptr),
+        DCG_ADVANCE_TABLE(true, true, nullptr, nullptr)};
+    if (ar_.cap > 0) fn = pre_kernels[lat][windowed][ps][S_.algo];
 #endif
 #undef DCG_ADVANCE_TABLE
 #undef DCG_ADVANCE_ROW
@@ -2655,6 +2672,7 @@ class BatchedSimHip {
   EngineDesc S_{};
   PopSeriesDesc ps_{};            // samples == nullptr: feature off
   ArrRing ar_{};                  // cap == 0: arrivals drawn in the kernel
+  LatHistDesc lh_{};              // hist == nullptr: feature off
   // launch plan (launch_plan.hpp)
   int forced_capacity_ = 0;       // 0: the runtime's occupancy answer
   int queried_capacity_ = 0;      // cache of that answer
@@ -2703,6 +2721,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "every) -> stats[T,C,5] f64 = {n, mean, M2, min, max}; replica r "
         "counts at tick t iff ticks[r] / every > t",
         py::arg("samples"), py::arg("ticks"), py::arg("every"));
+  m.def("latency_reduce", &dcg::latency_reduce,
+        "latency-histogram reduction (hist[R,D,2,256] i32, over[R,D,2] i32, "
+        "qs[Q] f64, 1 <= Q <= 8) -> (pop_hist[C',256] i64, "
+        "per_rep[C',Q+2,R] f64 = {quantiles, sla_miss_frac, jobs}, "
+        "stats[C',Q+2,5] f64 = {n, mean, M2, min, max} over non-NaN "
+        "replicas); C' = (D + 1) * 2, row D = sum over DCs",
+        py::arg("hist"), py::arg("over"), py::arg("qs"));
   m.def("rl_forward_mfma", &dcg::rl_forward_mfma,
         "MFMA (matrix-core) batched actor forward "
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",

@@ -11,6 +11,8 @@ Extensions over the reference:
   --replicas N                       Monte-Carlo replicas (batched engine)
   --pop-series [EVERY]               per-tick mean/CI bands over the replica
                                      ensemble (batched engine)
+  --latency-hist                     latency tail quantiles and SLA misses
+                                     over the replica ensemble (batched engine)
   --eco-objective is actually honored (the reference parses but drops it,
     SURVEY Appendix A.4), and --elastic-scaling is a store_true flag that
     really enables elastic scaling (the reference's type=bool flag could
@@ -92,6 +94,13 @@ def parse_args(argv=None):
                         "EVERY-th log tick and write the per-tick population "
                         "statistics to <out>/population/population_series.csv "
                         "(0 = off).")
+    p.add_argument("--latency-hist", action="store_true", default=False,
+                   help="Batched engine only: every replica histograms its "
+                        "job latencies per DC and job type; writes tail "
+                        "quantiles and SLA-miss fractions with confidence "
+                        "bands over the replicas to <out>/population/"
+                        "latency_quantiles.csv and the pooled histogram to "
+                        "latency_hist.csv (SLA: --sla_p99_ms).")
     p.add_argument("--rl-serve", type=str, default="device",
                    choices=["device", "host"],
                    help="chsac_af policy serving on the batched engine: "
@@ -180,6 +189,7 @@ def main(argv=None):
                             fp32_coeff_eval=args.fp32_coeff_eval,
                             pop_series=args.pop_series > 0,
                             pop_series_every=max(1, args.pop_series),
+                            latency_hist=args.latency_hist,
                             **common)
     else:
         from distributed_cluster_gpus_amd.engine.oracle import OracleEngine
@@ -207,6 +217,13 @@ def main(argv=None):
             eng, out_dir=os.path.join(out_dir, "population"))
         print(f"[population] time series: {sdf['time_s'].nunique()} ticks -> "
               f"{os.path.join(out_dir, 'population', 'population_series.csv')}")
+    if args.engine == "batched" and args.latency_hist:
+        from distributed_cluster_gpus_amd.analysis.montecarlo import \
+            latency_report
+        latency_report(eng, out_dir=os.path.join(out_dir, "population"),
+                       logger=logger)
+        print("[population] latency quantiles -> "
+              f"{os.path.join(out_dir, 'population', 'latency_quantiles.csv')}")
     if args.rl_checkpoint and getattr(eng, "rl", None) is not None:
         eng.rl.save(args.rl_checkpoint)
         print(f"RL checkpoint saved to {args.rl_checkpoint}")
