@@ -460,3 +460,175 @@ def latency_report(engine, out_dir: str, quantiles=DEFAULT_QUANTILES,
         log.info(f"latency_hist: {name} pooled p99 <= {p99[j]:.4g} s over "
                  f"{int(jobs[j])} jobs, SLA {stats.sla_s:g} s: {verdict}")
     return df
+
+
+# ---------------------------------------------------------------------------
+# Parameter sweeps: per-group statistics of the headline outcomes
+# (BatchedEngine(sweep=Sweep); engine/sweep.py)
+# ---------------------------------------------------------------------------
+SWEEP_METRICS = ["total_energy_j", "jobs", "jobs_inf", "mean_latency_s",
+                 "mean_inf_latency_s", "mean_wait_s", "events"]
+
+
+def sweep_replica_metrics(t) -> np.ndarray:
+    """[R, len(SWEEP_METRICS)] f64 from the host copies of the engine's
+    metric tensors.  A replica without a finished (inference) job has no mean
+    latency or wait: NaN there."""
+    jobs = np.asarray(t["jobs_done"], dtype=np.float64)
+    jobs_inf = np.asarray(t["jobs_done_inf"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cols = [
+            np.asarray(t["energy_j"], dtype=np.float64).sum(axis=1),
+            jobs, jobs_inf,
+            np.where(jobs > 0, np.asarray(t["sum_lat"]) / jobs, np.nan),
+            np.where(jobs_inf > 0, np.asarray(t["sum_lat_inf"]) / jobs_inf,
+                     np.nan),
+            np.where(jobs > 0, np.asarray(t["sum_wait"]) / jobs, np.nan),
+            np.asarray(t["ev_count"], dtype=np.float64),
+        ]
+    return np.stack(cols, axis=1)
+
+
+@dataclass
+class SweepStats:
+    """Per-group ensemble statistics of a sweep: ``n``, ``mean``, ``m2`` (sum
+    of squared deviations from the mean), ``min`` and ``max`` are [G,
+    len(metrics)], each over the group's replicas that have the figure (NaN
+    cells are skipped, as in LatencyStats).  Cells with n == 0 hold NaN
+    mean/min/max and m2 == 0."""
+    n: np.ndarray
+    mean: np.ndarray
+    m2: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    metrics: List[str]
+
+    @classmethod
+    def from_values(cls, values, slices) -> "SweepStats":
+        """values: [R, K] per-replica figures; slices: one ``(a, b)`` replica
+        range per group (empty where this rank holds none of it).  Two-pass,
+        shifted by the mean: sum of (x - mean)^2."""
+        v = np.asarray(values, dtype=np.float64)
+        G, K = len(slices), v.shape[1]
+        n = np.zeros((G, K), np.int64)
+        mean, lo, hi = (np.full((G, K), np.nan) for _ in range(3))
+        m2 = np.zeros((G, K))
+        for g, (a, b) in enumerate(slices):
+            for k in range(K):
+                x = v[a:b, k]
+                x = x[~np.isnan(x)]
+                if x.size == 0:
+                    continue
+                mu = x.sum() / x.size
+                d = x - mu
+                n[g, k], mean[g, k] = x.size, mu
+                m2[g, k] = (d * d).sum()
+                lo[g, k], hi[g, k] = x.min(), x.max()
+        return cls(n, mean, m2, lo, hi, list(SWEEP_METRICS))
+
+    def to_array(self) -> np.ndarray:
+        """[G, K, 5] float64 = {n, mean, M2, min, max}."""
+        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
+                         self.min, self.max], axis=-1)
+
+    @classmethod
+    def from_array(cls, a, metrics=None) -> "SweepStats":
+        """Inverse of to_array."""
+        a = np.asarray(a, dtype=np.float64)
+        return cls(a[..., 0].astype(np.int64), a[..., 1].copy(),
+                   a[..., 2].copy(), a[..., 3].copy(), a[..., 4].copy(),
+                   list(metrics if metrics is not None else SWEEP_METRICS))
+
+
+def _merge_sweep_pair(a: SweepStats, b: SweepStats) -> SweepStats:
+    assert a.metrics == b.metrics and a.n.shape == b.n.shape
+    mean, m2 = _chan(a, b)
+    return SweepStats(a.n + b.n, mean, m2, np.fmin(a.min, b.min),
+                      np.fmax(a.max, b.max), a.metrics)
+
+
+def merge_sweep_stats(parts: Sequence[SweepStats]) -> SweepStats:
+    """Combine the per-group statistics of disjoint replica sets (shards,
+    ranks, separate runs of one sweep): the Chan formula of
+    merge_series_stats per group and metric, in the same tree order; min and
+    max directly."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_sweep_stats needs at least one SweepStats")
+    return _tree_merge(parts, _merge_sweep_pair)
+
+
+SWEEP_STAT_COLUMNS = ["n", "mean", "stderr", "ci_lo", "ci_hi"]
+
+
+def sweep_frame(stats: SweepStats, sweep, confidence: float = 0.95,
+                base=None) -> pd.DataFrame:
+    """One row per group: ``group``, its parameters (``sweep.frame``), then
+    ``<metric>_n / _mean / _stderr / _ci_lo / _ci_hi`` per metric, with the
+    normal-approximation confidence interval over the group's replicas; zero
+    width when n < 2."""
+    z = _z(confidence)
+    df = sweep.frame(base)
+    if len(df) != stats.n.shape[0]:
+        raise ValueError(f"sweep has {len(df)} groups, the statistics "
+                         f"{stats.n.shape[0]}")
+    multi = stats.n > 1
+    std = np.where(multi, np.sqrt(np.maximum(stats.m2, 0.0)
+                                  / np.where(multi, stats.n - 1, 1)), 0.0)
+    se = np.where(multi, std / np.sqrt(np.where(multi, stats.n, 1)), 0.0)
+    for k, m in enumerate(stats.metrics):
+        df[f"{m}_n"] = stats.n[:, k]
+        df[f"{m}_mean"] = stats.mean[:, k]
+        df[f"{m}_stderr"] = se[:, k]
+        df[f"{m}_ci_lo"] = stats.mean[:, k] - z * se[:, k]
+        df[f"{m}_ci_hi"] = stats.mean[:, k] + z * se[:, k]
+    return df
+
+
+def sweep_report(engine, out_dir: str, confidence: float = 0.95,
+                 quantiles=DEFAULT_QUANTILES) -> pd.DataFrame:
+    """Write ``population/sweep.csv`` under ``out_dir``: one row per group
+    (``sweep_frame``); with ``latency_hist`` on also the group's pooled fleet
+    quantiles and mean SLA-miss fraction per job type; and one figure, energy
+    against the sweep's first axis.  Per-group latency columns come from this
+    rank's replicas.  Returns the frame."""
+    import os
+
+    from .render import emit
+    sweep = engine.sweep
+    df = sweep_frame(engine.sweep_stats(), sweep, confidence,
+                     engine.sweep_base)
+    if engine.dims.lat_hist:
+        cols = {}
+        for g in range(sweep.n_groups):
+            a, b = sweep.slice_of(g, engine.shard)
+            ls = engine.latency_distribution(quantiles, group=g) \
+                if b > a else None
+            for j, jt in enumerate(JOB_TYPES):
+                for q in quantiles:
+                    cols.setdefault(f"{jt}_{quantile_label(q)}_s", []).append(
+                        ls.pooled_quantile(q)[-1, j] if ls else np.nan)
+                k = len(quantiles)   # sla_miss_frac follows the quantiles
+                cols.setdefault(f"{jt}_sla_miss_frac", []).append(
+                    ls.mean[-1, j, k] if ls else np.nan)
+        for name, col in cols.items():
+            df[name] = col
+    pop_dir = os.path.join(out_dir, "population")
+    os.makedirs(pop_dir, exist_ok=True)
+    df.to_csv(os.path.join(pop_dir, "sweep.csv"), index=False)
+    axis = sweep.axes[0]
+    rest = [a for a in sweep.axes[1:]]
+    fig = df[[axis, "total_energy_j_mean", "total_energy_j_ci_lo",
+              "total_energy_j_ci_hi"] + rest].rename(columns={
+                  "total_energy_j_mean": "mean",
+                  "total_energy_j_ci_lo": "ci_lo",
+                  "total_energy_j_ci_hi": "ci_hi"})
+    hue = None
+    if rest:
+        fig["point"] = fig[rest].astype(str).agg(", ".join, axis=1)
+        hue = "point"
+    emit(fig, pop_dir, f"sweep_energy_vs_{axis}", kind="band", x=axis,
+         y="mean", hue=hue, ylabel="J",
+         title=f"Energy per replica against {axis}, mean and "
+               f"{confidence:.0%} CI per group")
+    return df

@@ -73,6 +73,72 @@ def raise_on_err(err: int, some_rank: bool = False):
                            f"(queue/transfer/slot/log overflow)")
 
 
+def raise_on_group_err(err_per_replica, sweep, shard):
+    """``raise_on_err`` for a sweep engine: the same failure, naming the
+    groups whose replicas carry error flags (the hottest point of a load
+    sweep is the one that overflows ``qcap``).  ``err_per_replica`` is this
+    rank's ``err`` tensor or array."""
+    err = np.asarray(err_per_replica.cpu() if hasattr(err_per_replica, "cpu")
+                     else err_per_replica)
+    if not err.any():
+        return
+    bad = []
+    for g in range(sweep.n_groups):
+        a, b = sweep.slice_of(g, shard)
+        flags = int(np.bitwise_or.reduce(err[a:b])) if b > a else 0
+        if flags:
+            bad.append(f"group {g} ({sweep.point(g)}): {flags:#x} on "
+                       f"{int((err[a:b] != 0).sum())} of {b - a} replicas")
+    raise RuntimeError(
+        f"batched engine error flags: {int(np.bitwise_or.reduce(err)):#x} "
+        "(queue/transfer/slot/log overflow) in sweep " + "; ".join(bad))
+
+
+def seed_arrivals(n_ing, procs_of_replica, seed, shard):
+    """Host-side Philox draws for the initial inter-arrival per stream,
+    matching the device recipe (philox.hpp).  ``procs_of_replica(r)`` is
+    local replica r's ``(arrival_inf, arrival_trn)``: one shared pair for a
+    uniform engine, the replica's own parameters under a sweep."""
+    from ._philox_host import philox_u01, replica_key, rexp
+    R = shard.count
+    NS = n_ing * 2
+    out = np.full((R, NS), INF)
+    for r in range(R):
+        key = replica_key(seed, shard.start + r)
+        arrival_inf, arrival_trn = procs_of_replica(r)
+        ctr = 0
+        for s in range(NS):
+            jt = s & 1
+            arr = arrival_inf if jt == 0 else arrival_trn
+            # the kernel reserves one counter per stream for the seed draw;
+            # thinning may need more draws -> sub-counter space: we use
+            # counter = stream index, and for extra thinning draws we
+            # borrow high bits (replica-unique; never reused by the device
+            # which starts at ctr = NS).
+            if arr.mode == "off" or arr.rate <= 0:
+                ctr += 1
+                continue
+            if arr.mode == "poisson":
+                out[r, s] = rexp(key, ctr, arr.rate)
+                ctr += 1
+            else:  # sinusoid thinning at t=0
+                max_rate = arr.rate * (1.0 + abs(arr.amp))
+                sub = 0
+                ia = INF
+                while sub < 4096:
+                    w = rexp(key, ctr + ((sub * 2 + 1) << 32), max_rate)
+                    lam = max(0.0, arr.rate * (1.0 + arr.amp * math.sin(
+                        2.0 * math.pi * (w % arr.period) / arr.period)))
+                    u2 = philox_u01(key, ctr + ((sub * 2 + 2) << 32))
+                    if u2 <= lam / max_rate:
+                        ia = w
+                        break
+                    sub += 1
+                out[r, s] = ia
+                ctr += 1
+    return out
+
+
 class BatchedEngine:
     def __init__(self, scenario: Scenario,
                  arrival_inf: ArrivalProcess, arrival_trn: ArrivalProcess,
@@ -103,11 +169,24 @@ class BatchedEngine:
                  arrival_pregen: bool = True, arr_cap: int = ARR_CAP,
                  latency_hist: bool = False,
                  latency_sla_s: Optional[float] = None,
+                 sweep=None,
                  **_unused):
         if algo not in ALGOS:
             raise ValueError(f"unknown algo {algo!r}")
         if pop_series and int(pop_series_every) < 1:
             raise ValueError("pop_series_every must be >= 1")
+        # parameter sweep (engine/sweep.py): G groups of replicas, each at
+        # its own arrival parameters / power cap
+        self.sweep = sweep
+        self.sweep_base = None
+        if sweep is not None:
+            from .sweep import SweepBase
+            self.sweep_base = SweepBase.of(arrival_inf, arrival_trn, power_cap)
+            sweep.validate(base=self.sweep_base, algo=algo,
+                           replicas=int(replicas),
+                           arrival_trace=arrival_trace,
+                           arrival_pregen=bool(arrival_pregen),
+                           subwave=subwave)
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedEngine requires a ROCm GPU "
                                "(no silent CPU fallback)")
@@ -180,7 +259,7 @@ class BatchedEngine:
             # and stays the independent reference
             arrival_pregen=bool(arrival_pregen) and subwave == 64,
             arr_cap=arr_cap, latency_hist=latency_hist,
-            latency_sla_s=latency_sla_s)
+            latency_sla_s=latency_sla_s, sweep=sweep)
         self.dims = dims
         if dims.lat_hist:
             lh_bytes = R * n_dc * 2 * (LH_BINS + 1) * 4
@@ -194,13 +273,19 @@ class BatchedEngine:
                 f"pop_series: sample buffer {dims.ps_cap} ticks x {n_dc + 1} "
                 f"rows x {len(SERIES_METRICS)} metrics x {R} replicas x 8 B = "
                 f"{ps_bytes} bytes ({ps_bytes / 2**20:.1f} MiB)")
-        t = alloc_state(dims, scenario, dev, arrival_trace)
+        sweep_table = sweep.table(shard, self.sweep_base) \
+            if sweep is not None else None
+        t = alloc_state(dims, scenario, dev, arrival_trace, sweep_table)
         if not self.trace_mode:
             # seed the initial arrival times on host (one inf + one trn per
             # ingress per replica), Philox-consistent with the device streams:
             # the kernel's first draws start at ctr = n_streams; host uses
-            # ctr = stream index for the seed draws.
-            arr_np = self._seed_arrivals(arrival_inf, arrival_trn, seed, shard)
+            # ctr = stream index for the seed draws.  Under a sweep each
+            # replica's draws use its own rate, amp and period.
+            arr_np = self._seed_arrivals(arrival_inf, arrival_trn, seed, shard) \
+                if sweep is None else seed_arrivals(
+                    scenario.n_ing, self._sweep_procs(
+                        arrival_inf, arrival_trn, sweep_table[0]), seed, shard)
             t["arr_next"].copy_(torch.as_tensor(arr_np, dtype=torch.float64))
         self.t = t
         self.arrival_inf, self.arrival_trn = arrival_inf, arrival_trn
@@ -242,45 +327,22 @@ class BatchedEngine:
         self._rl_drv.mfma_serve = on
 
     def _seed_arrivals(self, arrival_inf, arrival_trn, seed, shard):
-        """Host-side Philox draws for the initial inter-arrival per stream,
-        matching the device recipe (philox.hpp)."""
-        from ._philox_host import philox_u01, replica_key, rexp
-        R = shard.count
-        NS = self.sc.n_ing * 2
-        out = np.full((R, NS), INF)
-        for r in range(R):
-            key = replica_key(seed, shard.start + r)
-            ctr = 0
-            for s in range(NS):
-                jt = s & 1
-                arr = arrival_inf if jt == 0 else arrival_trn
-                # the kernel reserves one counter per stream for the seed draw;
-                # thinning may need more draws -> sub-counter space: we use
-                # counter = stream index, and for extra thinning draws we
-                # borrow high bits (replica-unique; never reused by the device
-                # which starts at ctr = NS).
-                if arr.mode == "off" or arr.rate <= 0:
-                    ctr += 1
-                    continue
-                if arr.mode == "poisson":
-                    out[r, s] = rexp(key, ctr, arr.rate)
-                    ctr += 1
-                else:  # sinusoid thinning at t=0
-                    max_rate = arr.rate * (1.0 + abs(arr.amp))
-                    sub = 0
-                    ia = INF
-                    while sub < 4096:
-                        w = rexp(key, ctr + ((sub * 2 + 1) << 32), max_rate)
-                        lam = max(0.0, arr.rate * (1.0 + arr.amp * math.sin(
-                            2.0 * math.pi * (w % arr.period) / arr.period)))
-                        u2 = philox_u01(key, ctr + ((sub * 2 + 2) << 32))
-                        if u2 <= lam / max_rate:
-                            ia = w
-                            break
-                        sub += 1
-                    out[r, s] = ia
-                    ctr += 1
-        return out
+        """The seed draws of an engine whose replicas share one arrival pair
+        (``seed_arrivals`` below)."""
+        return seed_arrivals(self.sc.n_ing,
+                             lambda r: (arrival_inf, arrival_trn), seed, shard)
+
+    def _sweep_procs(self, arrival_inf, arrival_trn, sw_arr):
+        """``procs_of_replica`` of a sweep: the base pair's modes with the
+        replica's own rate, amp and period (``sw_arr`` [R, 2, 3])."""
+        import dataclasses
+
+        def procs(r):
+            return tuple(dataclasses.replace(
+                base, rate=float(sw_arr[r, jt, 0]), amp=float(sw_arr[r, jt, 1]),
+                period=float(sw_arr[r, jt, 2]))
+                for jt, base in enumerate((arrival_inf, arrival_trn)))
+        return procs
 
     # ---------------- run ----------------
     def run(self, max_wall_s: Optional[float] = None):
@@ -318,6 +380,8 @@ class BatchedEngine:
             self.timing["launches"] += 1
             st = read_status(self.t, ("err", "done", "n_jl"))
         with Lap(self.timing, "serve_s"):
+            if st["err"] != 0 and self.sweep is not None:
+                raise_on_group_err(self.t["err"], self.sweep, self.shard)
             raise_on_err(st["err"])
             self._drain_job_rows(st["n_jl"])
         return st["done"] == 1
@@ -373,26 +437,75 @@ class BatchedEngine:
         return {"samples": t["ps_samples"], "ticks": t["ps_tick"],
                 "time": t["ps_time"]}
 
-    def population_series(self):
+    # ---------------- parameter sweep ----------------
+    def _group_slice(self, group):
+        """Local replica range ``[a, b)`` of sweep group ``group``."""
+        if self.sweep is None:
+            raise RuntimeError("engine was built without sweep=")
+        return self.sweep.slice_of(int(group), self.shard)
+
+    def sweep_stats(self):
+        """Per-group statistics of the headline outcomes as a SweepStats
+        (analysis/montecarlo.py): n / mean / M2 / min / max over each group's
+        replicas of total energy, jobs, inference jobs, mean latency, mean
+        inference latency, mean wait and events.  R x 7 numbers: numpy f64 on
+        the host.  Under torch.distributed the per-rank statistics are
+        merged, so every rank holds the global ones."""
+        from ..analysis.montecarlo import (SWEEP_METRICS, SweepStats,
+                                           merge_sweep_stats,
+                                           sweep_replica_metrics)
+        from ..parallel.dist import allgather_series_stats, is_distributed
+        if self.sweep is None:
+            raise RuntimeError("engine was built without sweep=")
+        vals = sweep_replica_metrics({k: self.t[k].cpu().numpy() for k in (
+            "energy_j", "jobs_done", "jobs_done_inf", "sum_lat",
+            "sum_lat_inf", "sum_wait", "ev_count")})
+        G = self.sweep.n_groups
+        mine = SweepStats.from_values(
+            vals, [self.sweep.slice_of(g, self.shard) for g in range(G)])
+        if not (self.world > 1 and is_distributed()):
+            return mine
+        parts = allgather_series_stats(
+            torch.from_numpy(mine.to_array().reshape(-1)))
+        return merge_sweep_stats(
+            [SweepStats.from_array(
+                p.cpu().numpy().reshape(G, len(SWEEP_METRICS), 5))
+             for p in parts])
+
+    def population_series(self, group=None):
         """Per-tick statistics over the replica ensemble as a SeriesStats
         (analysis/montecarlo.py): n, mean, M2, min, max of every sampled
         metric per DC and fleet-wide, trimmed to the ticks at least one
         replica has reached.  Valid on an unfinished run (n counts the
         replicas that reached each tick).  Under torch.distributed the
         per-rank statistics are merged, so every rank holds the global
-        series."""
+        series.  ``group=g`` (sweep engines): over that group's replicas on
+        this rank only."""
         from ..analysis.montecarlo import SeriesStats, merge_series_stats
         from ..parallel.dist import allgather_series_stats, is_distributed
         ps = self.pop_samples()
         every = self.pop_series_every
         cap = int(ps["samples"].shape[0])
+        n_row, K = self.sc.n_dc + 1, len(SERIES_METRICS)
+        names = list(self.sc.dc_names) + [SERIES_FLEET]
+        if group is not None:
+            a, b = self._group_slice(group)
+            if b <= a:
+                raise ValueError(f"this rank holds no replica of group {group}")
+            ticks = ps["ticks"][a:b].contiguous()
+            T = min(cap, int(ticks.max().item()) // every)
+            # replica-minor buffer: the group's columns, packed
+            smp = ps["samples"][:T, :, :, a:b].contiguous()
+            raw = self._mod.reduce_series(
+                smp.view(T, n_row * K, b - a), ticks, every)
+            return SeriesStats.from_tensor(
+                raw.cpu().view(T, n_row, K, 5), ps["time"][:T].cpu(),
+                metrics=list(SERIES_METRICS), dc_names=names).trimmed()
         dist_on = self.world > 1 and is_distributed()
         # ranks must agree on the shape they gather: the full buffer then
         T = cap if dist_on else min(cap, int(ps["ticks"].max().item()) // every)
-        n_row, K = self.sc.n_dc + 1, len(SERIES_METRICS)
         raw = self._mod.reduce_series(
             ps["samples"][:T].view(T, n_row * K, self.R), ps["ticks"], every)
-        names = list(self.sc.dc_names) + [SERIES_FLEET]
 
         def wrap(flat_stats, time):
             return SeriesStats.from_tensor(
@@ -416,25 +529,33 @@ class BatchedEngine:
         return {"hist": self.t["lh_hist"], "over": self.t["lh_over"],
                 "sla_s": self.dims.lat_sla_s}
 
-    def latency_distribution(self, quantiles=(0.5, 0.9, 0.99, 0.999)):
+    def latency_distribution(self, quantiles=(0.5, 0.9, 0.99, 0.999),
+                             group=None):
         """Latency quantiles, SLA-miss fraction and job count per (DC, job
         type) and fleet-wide as a LatencyStats (analysis/montecarlo.py): the
         histogram pooled over the replicas, and n / mean / M2 / min / max of
         every per-replica figure over the replicas that have one.  Valid on an
         unfinished run.  Under torch.distributed the per-rank results are
-        merged, so every rank holds the global one."""
+        merged, so every rank holds the global one.  ``group=g`` (sweep
+        engines): over that group's replicas on this rank only."""
         from ..analysis.montecarlo import LatencyStats, merge_latency_stats
         from ..parallel.dist import allgather_series_stats, is_distributed
         lh = self.latency_hist()
         qs = [float(q) for q in quantiles]
+        hist, over = lh["hist"], lh["over"]
+        if group is not None:
+            a, b = self._group_slice(group)
+            if b <= a:
+                raise ValueError(f"this rank holds no replica of group {group}")
+            hist, over = hist[a:b], over[a:b]   # replica-major: contiguous
         pop, _, stats = self._mod.latency_reduce(
-            lh["hist"], lh["over"], torch.tensor(qs, dtype=torch.float64))
+            hist, over, torch.tensor(qs, dtype=torch.float64))
         names = list(self.sc.dc_names) + [SERIES_FLEET]
         n_row, K = len(names), len(qs) + 2
         mine = LatencyStats.from_tensor(
             pop.cpu().view(n_row, 2, LH_BINS), stats.cpu().view(n_row, 2, K, 5),
             quantiles=qs, dc_names=names, sla_s=lh["sla_s"])
-        if not (self.world > 1 and is_distributed()):
+        if group is not None or not (self.world > 1 and is_distributed()):
             return mine
         # the histogram travels as f64 with the statistics: exact below 2^53
         parts = allgather_series_stats(torch.from_numpy(mine.to_flat()))
@@ -457,6 +578,17 @@ class BatchedEngine:
 
     def load_state(self, path: str):
         st = torch.load(path, map_location="cpu", weights_only=False)
+        # a sweep's parameters are state: a checkpoint of another sweep (or
+        # of other base values) would silently change this engine's points
+        for k in ("sw_arr", "sw_cap"):
+            if k in self.t and k in st["tensors"] and \
+                    tuple(st["tensors"][k].shape) == tuple(self.t[k].shape) \
+                    and not torch.equal(st["tensors"][k].to(self.t[k].dtype),
+                                        self.t[k].cpu()):
+                raise ValueError(
+                    f"checkpoint tensor {k!r} differs from this engine's own "
+                    "sweep: it was saved by an engine with other parameter "
+                    "points")
         load_tensors(self.t, st["tensors"])
         if self._rl_drv is not None:
             self._rl_drv.rl_updates = st.get("rl_updates", 0)

@@ -92,6 +92,8 @@ class EngineDims:
     arr_cap: int = 0            # arrival ring: records per replica; 0 = off
     lat_hist: bool = False      # per-replica latency histograms
     lat_sla_s: float = 0.5      # ... and the sojourn their SLA-miss count uses
+    sweep: bool = False         # parameter sweep (engine/sweep.py): sw_* exist
+    sweep_cap: bool = False     # ... and it has a power_cap axis
 
     @property
     def is_rl(self) -> bool:
@@ -126,7 +128,8 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
                 rl_train_interval: int = 256,
                 arrival_pregen: bool = True,
                 arr_cap: int = ARR_CAP, latency_hist: bool = False,
-                latency_sla_s: Optional[float] = None) -> EngineDims:
+                latency_sla_s: Optional[float] = None,
+                sweep=None) -> EngineDims:
     """``n_rep`` is this rank's replica count; ``serve_device`` /
     ``weights_buffer`` say whether the kernel serves the policy itself and
     whether the flat actor-weights buffer is needed at all (it also feeds the
@@ -134,7 +137,8 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
     ring of ``arr_cap`` records (a power of two) per replica; chsac_af and
     trace mode never have one.  ``latency_hist`` asks for the per-replica
     latency histograms; ``latency_sla_s`` (default ``sla_p99_ms / 1000``) is
-    the sojourn above which a finish counts as an SLA miss."""
+    the sojourn above which a finish counts as an SLA miss.  ``sweep`` (a
+    ``Sweep``) records that a parameter sweep is on; it needs the ring."""
     is_rl = algo == "chsac_af"
     n_dc = scenario.n_dc
     end_time, log_interval = float(duration), float(log_interval)
@@ -154,6 +158,13 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
     pregen = bool(arrival_pregen) and not is_rl and arrival_trace is None
     if pregen and (int(arr_cap) < 1 or int(arr_cap) & (int(arr_cap) - 1)):
         raise ValueError(f"arr_cap must be a power of two, got {arr_cap}")
+    if sweep is not None and not pregen:
+        raise ValueError("a sweep lives in the arrival-ring generator: it "
+                         "needs arrival_pregen, no arrival_trace and an algo "
+                         "other than chsac_af")
+    if sweep is not None and sweep.has_power_cap and algo != "cap_greedy":
+        raise ValueError("a power_cap sweep axis needs algo='cap_greedy', "
+                         f"got {algo!r}")
     return EngineDims(
         algo=algo, n_rep=int(n_rep), n_dc=n_dc, n_ing=scenario.n_ing,
         n_freq=scenario.n_freq,
@@ -187,15 +198,19 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
         arr_cap=int(arr_cap) if pregen else 0,
         lat_hist=bool(latency_hist),
         lat_sla_s=float(latency_sla_s) if latency_sla_s is not None
-        else float(sla_p99_ms) / 1000.0)
+        else float(sla_p99_ms) / 1000.0,
+        sweep=sweep is not None,
+        sweep_cap=sweep is not None and sweep.has_power_cap)
 
 
 def alloc_state(dims: EngineDims, scenario: Scenario, device,
-                arrival_trace=None) -> dict:
+                arrival_trace=None, sweep_table=None) -> dict:
     """The engine's tensors by EngineDesc field name, in their initial state.
     ``arr_next`` holds the trace's first arrivals in trace mode and +inf
     otherwise (the caller seeds it); ``rng_ctr`` starts past the one counter
-    block per stream that seeding consumes."""
+    block per stream that seeding consumes.  ``sweep_table`` is the ``(arr,
+    cap)`` pair of ``Sweep.table`` for this rank's replicas, required exactly
+    when ``dims.sweep``."""
     d = dims
     dev = torch.device(device)
     R, n_dc, n_freq, NS = d.n_rep, d.n_dc, d.n_freq, d.n_streams
@@ -326,6 +341,21 @@ def alloc_state(dims: EngineDims, scenario: Scenario, device,
     if d.lat_hist:
         t["lh_hist"] = torch.zeros((R, n_dc, 2, LH_BINS), **i32)
         t["lh_over"] = torch.zeros((R, n_dc, 2), **i32)
+
+    # parameter sweep (opt-in): every replica's own arrival parameters and
+    # power cap, constant over the run.  sw_arr is read by the arrival-ring
+    # generator, sw_cap by the cap_greedy kernel where the sweep has a
+    # power_cap axis (elsewhere it holds the base cap and nobody reads it)
+    if d.sweep != (sweep_table is not None):
+        raise ValueError("alloc_state: sweep_table goes with dims.sweep")
+    if d.sweep:
+        sw_arr, sw_cap = (np.asarray(x, np.float64) for x in sweep_table)
+        if sw_arr.shape != (R, 2, 3) or sw_cap.shape != (R,):
+            raise ValueError(
+                f"sweep table is {sw_arr.shape} / {sw_cap.shape}, this rank's "
+                f"{R} replicas need {(R, 2, 3)} / {(R,)}")
+        t["sw_arr"] = T(sw_arr, dtype=torch.float64)
+        t["sw_cap"] = T(sw_cap, dtype=torch.float64)
 
     # arrival-trace replay mode (exact single-replica parity testing):
     # arrivals come from a recorded (time, size) FIFO per stream
@@ -458,4 +488,5 @@ def engine_cfg(dims: EngineDims, scenario: Scenario, arrival_inf,
         "tr_limit": d.tr_limit, "exact_p99": d.exact_p99,
         "p99_win": P99_WIN, "pop_series_every": d.ps_every,
         "arr_cap": d.arr_cap, "lat_sla_s": d.lat_sla_s,
+        "sweep_cap": int(d.sweep_cap),
     }

@@ -83,9 +83,14 @@ __device__ __forceinline__ int pg_group_ballot(bool p, int lane64) {
 // empty ring the frontier IS the consumed state, so it is re-read from
 // S.arr_next / S.rng_ctr (which also covers the first launch of a run and a
 // host that rewrote those tensors between runs).
+//
+// SWP: a parameter sweep is on (SweepDesc): rate, amplitude and period are
+// the replica's own, loaded once per lane before the walk, instead of the
+// EngineDesc scalars.  The modes are not swept.  SWP = false never looks at W.
+template <bool SWP>
 __global__ void __launch_bounds__(PG_THREADS)
 pregen_arrivals_kernel(EngineDesc S, ArrRing A, double t_target,
-                       long long budget) {
+                       long long budget, SweepDesc W) {
   const int r = (int)((blockIdx.x * (unsigned)PG_THREADS + threadIdx.x) /
                       PG_GROUP);
   const int gl = threadIdx.x & (PG_GROUP - 1);
@@ -108,6 +113,15 @@ pregen_arrivals_kernel(EngineDesc S, ArrRing A, double t_target,
     if (2 * gl < NS) s0 = an[2 * gl];
     if (2 * gl + 1 < NS) s1 = an[2 * gl + 1];
     key = S.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(S.rep_id_offset + r));
+  }
+  // SWP: the replica's own arrival parameters by job type, six registers
+  // (a dead lane never walks)
+  double rate0 = 0.0, rate1 = 0.0, amp0 = 0.0, amp1 = 0.0;
+  double period0 = 1.0, period1 = 1.0;
+  if (SWP && live) {
+    const double* sw = W.arr + (int64_t)r * 6;
+    rate0 = sw[0]; amp0 = sw[1]; period0 = sw[2];
+    rate1 = sw[3]; amp1 = sw[4]; period1 = sw[5];
   }
 
   // the arrival this lane finishes at the next flush
@@ -165,10 +179,14 @@ pregen_arrivals_kernel(EngineDesc S, ArrRing A, double t_target,
       // inter-arrival time: draw_interarrival's cases, its counters
       // (selects, not S.arr_*[jt]: jt differs between the groups of a wave,
       // and a lane-indexed kernel argument would be copied to scratch)
-      const double rate = jt ? S.arr_rate[1] : S.arr_rate[0];
+      // (SWP: the same selects between the replica's registers)
+      const double rate = SWP ? (jt ? rate1 : rate0)
+                              : (jt ? S.arr_rate[1] : S.arr_rate[0]);
       const int mode = jt ? S.arr_mode[1] : S.arr_mode[0];
-      const double amp = jt ? S.arr_amp[1] : S.arr_amp[0];
-      const double period = jt ? S.arr_period[1] : S.arr_period[0];
+      const double amp = SWP ? (jt ? amp1 : amp0)
+                             : (jt ? S.arr_amp[1] : S.arr_amp[0]);
+      const double period = SWP ? (jt ? period1 : period0)
+                                : (jt ? S.arr_period[1] : S.arr_period[0]);
       const double lambd = mode == 1 ? rate * (1.0 + fabs(amp)) : rate;
       double ia = D_INF;
       if ((mode == 0 || mode == 1) && lambd > 0) {

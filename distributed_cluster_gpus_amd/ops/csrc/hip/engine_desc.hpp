@@ -283,6 +283,17 @@ struct ArrRing {
                                   //   same call may still have work
 };
 
+// A parameter sweep (engine/sweep.py): per-replica arrival parameters and
+// power cap in place of the EngineDesc scalars of the same names.  Per
+// replica, not per group plus an index: one load, no second indirection.
+// Read by pregen_arrivals_kernel<true> (arr) and by the SWP instantiations
+// of the cap_greedy advance kernel (cap); written by nobody on the device.
+// A trailing kernel argument of its own, as ArrRing is.  null: off.
+struct SweepDesc {
+  const double* arr;              // [r][2][3] (jtype; rate, amp, period)
+  const double* cap;              // [r] power cap; null: no power_cap axis
+};
+
 // the Python side allocates the records as float64 rows (s_rec [.., 8],
 // x_rec and arr_ring [.., 4]); the binder casts those rows to the record types
 static_assert(sizeof(SRec) == 8 * sizeof(double), "s_rec rows are 8 f64 wide");

@@ -1330,10 +1330,17 @@ __device__ __attribute__((noinline)) void rl_realloc_inline(Ctx& c,
 // LAT: every job finish is counted into the replica's latency histogram
 // (lat_hist.hpp); its descriptor L is one more trailing argument, and the
 // LAT = false kernels never look at it
-template <int ALGO, bool PS, bool WIN, bool PRE = false, bool LAT = false>
+// SWP: a power_cap sweep (SweepDesc::cap): the log tick's cap control uses
+// the replica's own cap as S.power_cap.  Instantiated for cap_greedy
+// with PRE only; every kernel takes the trailing SW, the others ignore it
+// (an arrival-rate sweep lives in the generator and runs the SWP = false
+// kernels)
+template <int ALGO, bool PS, bool WIN, bool PRE = false, bool LAT = false,
+          bool SWP = false>
 __global__ void DCG_ADVANCE_BOUNDS
 advance_kernel(EngineDesc S, double t_target, long long max_ev,
-               PopSeriesDesc P, LaunchWindow W, ArrRing A, LatHistDesc L) {
+               PopSeriesDesc P, LaunchWindow W, ArrRing A, LatHistDesc L,
+               SweepDesc SW) {
   // SUBW lanes form one replica slot (64: wave-per-replica; 8: eight
   // replicas per wavefront)
   // (64-lane build: the slot, and with it the replica index and the event
@@ -1346,6 +1353,8 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
   static_assert(!(WIN && ALGO == A_CHSAC), "chsac has no windowed kernel");
   static_assert(!(PRE && (ALGO == A_CHSAC || SUBW != 64)),
                 "chsac draws at its arrivals; the 8-lane build has no ring");
+  static_assert(!SWP || (PRE && ALGO == A_CAP_GREEDY),
+                "only cap_greedy reads a swept cap, and only with the ring");
   if (slot_id >= (WIN ? W.count : S.n_rep)) return;
   // windowed: the event counter runs up to max_ev = W.ev_a for every slot, a
   // scalar bound in both builds; slots past the split start it at the
@@ -1386,6 +1395,12 @@ advance_kernel(EngineDesc S, double t_target, long long max_ev,
     ring_head = sub_uniform_i32(A.head[c.r]);
     ring_left = sub_uniform_i32(A.count[c.r]);
   }
+  // A power_cap sweep: the replica's own cap (c.r is wave-uniform: one
+  // scalar load) replaces power_cap in this kernel's by-value copy of the
+  // descriptor, the copy c.S points to.  The gate at the log tick and the
+  // out-of-line cap_greedy_control read it there as they always did, so that
+  // function is the one the SWP = false kernels call, unchanged and noinline.
+  if (SWP) S.power_cap = SW.cap[c.r];
 
   const int NS = S.n_streams;
   int64_t sbase = (int64_t)c.r * S.total_slots;
@@ -2402,6 +2417,22 @@ class BatchedSimHip {
       bind(lh_.hist, "lh_hist", R * D * 2 * LH_BINS);
       bind(lh_.over, "lh_over", R * D * 2);
     }
+    // parameter sweep (on where the host allocated its tensors): sw_arr is
+    // the generator's; sw_cap is the cap_greedy kernel's and dereferenced
+    // only where the sweep has a power_cap axis (cfg sweep_cap)
+    if (t_.count("sw_arr") != 0 || t_.count("sw_cap") != 0) {
+      const bool cap_axis = opt("sweep_cap", 0) != 0;
+      if (ar_.cap == 0)
+        throw std::invalid_argument(
+            "engine tensor 'sw_arr': a sweep lives in the arrival-ring "
+            "generator, required arr_cap > 0 in the 64-lane build");
+      if (cap_axis && S_.algo != A_CAP_GREEDY)
+        throw std::invalid_argument(
+            "engine tensor 'sw_cap': only cap_greedy reads a swept cap");
+      bind(sw_.arr, "sw_arr", R * 6);
+      if (cap_axis) bind(sw_.cap, "sw_cap", R);
+      else bind.unused("sw_cap");
+    }
     contract_ = bind.rows();
     on_gpu_ = bind.on_gpu();
     device_ = bind.device_str();
@@ -2557,10 +2588,12 @@ class BatchedSimHip {
       if (ar_.cap > 0) {
         // same stream, so the ring is topped up before the windows read it
         const int per_block = PG_THREADS / PG_GROUP;
-        hipLaunchKernelGGL(pregen_arrivals_kernel,
-                           dim3((S_.n_rep + per_block - 1) / per_block),
+        // a sweep's generator reads the replica's own arrival parameters
+        auto gen = sw_.arr ? pregen_arrivals_kernel<true>
+                           : pregen_arrivals_kernel<false>;
+        hipLaunchKernelGGL(gen, dim3((S_.n_rep + per_block - 1) / per_block),
                            dim3(PG_THREADS), 0, stream(), S_, ar_, t_target,
-                           ev);
+                           ev, sw_);
         check_launch("pregen_arrivals_kernel launch failed");
       }
 #endif
@@ -2569,7 +2602,7 @@ class BatchedSimHip {
       for (const LaunchWindow& w : plan.windows) {
         dim3 grid((w.count + rpb - 1) / rpb);
         hipLaunchKernelGGL(fn, grid, block, shmem, stream(), S_, t_target,
-                           w.ev_a, ps_, w, ar_, lh_);
+                           w.ev_a, ps_, w, ar_, lh_, sw_);
         check_launch("advance_kernel launch failed");
       }
     }
@@ -2607,7 +2640,7 @@ class BatchedSimHip {
   }
 
   using AdvanceFn = void (*)(EngineDesc, double, long long, PopSeriesDesc,
-                             LaunchWindow, ArrRing, LatHistDesc);
+                             LaunchWindow, ArrRing, LatHistDesc, SweepDesc);
 
   // this engine's instantiation: one per Algo, in enum order, without and
   // with the population-series sampling, without and with the window
@@ -2647,6 +2680,17 @@ class BatchedSimHip {
         DCG_ADVANCE_TABLE(true, false, nullptr, nullptr),
         DCG_ADVANCE_TABLE(true, true, nullptr, nullptr)};
     if (ar_.cap > 0) fn = pre_kernels[lat][windowed][ps][S_.algo];
+    // a power_cap sweep: cap_greedy with the replica's own cap
+    // [LAT][windowed][PS]
+#define DCG_SWEPT_CAP(PS, WIN, LAT)                                            \
+  advance_kernel<A_CAP_GREEDY, PS, WIN, true, LAT, true>
+    static const AdvanceFn swept_cap_kernels[2][2][2] = {
+        {{DCG_SWEPT_CAP(false, false, false), DCG_SWEPT_CAP(true, false, false)},
+         {DCG_SWEPT_CAP(false, true, false), DCG_SWEPT_CAP(true, true, false)}},
+        {{DCG_SWEPT_CAP(false, false, true), DCG_SWEPT_CAP(true, false, true)},
+         {DCG_SWEPT_CAP(false, true, true), DCG_SWEPT_CAP(true, true, true)}}};
+#undef DCG_SWEPT_CAP
+    if (sw_.cap != nullptr) fn = swept_cap_kernels[lat][windowed][ps];
 #endif
 #undef DCG_ADVANCE_TABLE
 #undef DCG_ADVANCE_ROW
@@ -2673,6 +2717,7 @@ class BatchedSimHip {
   PopSeriesDesc ps_{};            // samples == nullptr: feature off
   ArrRing ar_{};                  // cap == 0: arrivals drawn in the kernel
   LatHistDesc lh_{};              // hist == nullptr: feature off
+  SweepDesc sw_{};                // arr == nullptr: no parameter sweep
   // launch plan (launch_plan.hpp)
   int forced_capacity_ = 0;       // 0: the runtime's occupancy answer
   int queried_capacity_ = 0;      // cache of that answer

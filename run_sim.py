@@ -13,6 +13,9 @@ Extensions over the reference:
                                      ensemble (batched engine)
   --latency-hist                     latency tail quantiles and SLA misses
                                      over the replica ensemble (batched engine)
+  --sweep-inf-rate / --sweep-trn-rate / --sweep-power-cap A,B,..
+                                     a grid of parameter points inside one
+                                     replica ensemble (batched engine)
   --eco-objective is actually honored (the reference parses but drops it,
     SURVEY Appendix A.4), and --elastic-scaling is a store_true flag that
     really enables elastic scaling (the reference's type=bool flag could
@@ -101,6 +104,15 @@ def parse_args(argv=None):
                         "bands over the replicas to <out>/population/"
                         "latency_quantiles.csv and the pooled histogram to "
                         "latency_hist.csv (SLA: --sla_p99_ms).")
+    for flag, what in (("--sweep-inf-rate", "inference arrival rates"),
+                       ("--sweep-trn-rate", "training arrival rates"),
+                       ("--sweep-power-cap", "power caps in W (cap_greedy)")):
+        p.add_argument(flag, type=_float_list, default=None, metavar="A,B,..",
+                       help=f"Batched engine only: comma list of {what}; the "
+                            "--sweep-* lists together form a grid of "
+                            "parameter points, --replicas are split evenly "
+                            "over them, and per-point statistics go to "
+                            "<out>/population/sweep.csv.")
     p.add_argument("--rl-serve", type=str, default="device",
                    choices=["device", "host"],
                    help="chsac_af policy serving on the batched engine: "
@@ -122,7 +134,28 @@ def parse_args(argv=None):
                         "(chsac_af only).")
     p.add_argument("--rl-resume", type=str, default=None,
                    help="Path to an RL agent checkpoint to load before running.")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if sweep_axes(args) and args.engine != "batched":
+        p.error("--sweep-inf-rate / --sweep-trn-rate / --sweep-power-cap "
+                "need --engine batched")
+    return args
+
+
+def _float_list(text):
+    try:
+        vals = [float(x) for x in text.split(",") if x.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma list of numbers: {text!r}")
+    if not vals:
+        raise argparse.ArgumentTypeError("an empty list")
+    return vals
+
+
+def sweep_axes(args):
+    """The --sweep-* lists as Sweep.grid axes, in flag order ({} = no sweep)."""
+    given = (("inf_rate", args.sweep_inf_rate), ("trn_rate", args.sweep_trn_rate),
+             ("power_cap", args.sweep_power_cap))
+    return {name: vals for name, vals in given if vals is not None}
 
 
 def resolve_out_dir(log_path, algo):
@@ -182,7 +215,10 @@ def main(argv=None):
         eng = NativeEngine(sc, arrival_inf, arrival_trn, **common)
     elif args.engine == "batched":
         from distributed_cluster_gpus_amd.engine.batched import BatchedEngine
+        from distributed_cluster_gpus_amd.engine.sweep import Sweep
+        axes = sweep_axes(args)
         eng = BatchedEngine(sc, arrival_inf, arrival_trn,
+                            sweep=Sweep.grid(**axes) if axes else None,
                             replicas=args.replicas, rl_serve=args.rl_serve,
                             rl_exact_p99=args.rl_exact_p99,
                             rl_target_updates_per_s=args.rl_target_ups,
@@ -224,6 +260,12 @@ def main(argv=None):
                        logger=logger)
         print("[population] latency quantiles -> "
               f"{os.path.join(out_dir, 'population', 'latency_quantiles.csv')}")
+    if args.engine == "batched" and eng.sweep is not None:
+        from distributed_cluster_gpus_amd.analysis.montecarlo import \
+            sweep_report
+        wdf = sweep_report(eng, out_dir)
+        print(f"[population] sweep: {len(wdf)} parameter points -> "
+              f"{os.path.join(out_dir, 'population', 'sweep.csv')}")
     if args.rl_checkpoint and getattr(eng, "rl", None) is not None:
         eng.rl.save(args.rl_checkpoint)
         print(f"RL checkpoint saved to {args.rl_checkpoint}")
