@@ -14,6 +14,8 @@ A draw takes (key, ctr) and consumes exactly one counter, like its device
 twin; the `*_map` functions are the word -> value halves."""
 import math
 
+from ..models.arrivals import profile_gap  # noqa: F401  (the twin itself)
+
 M0 = 0xD2511F53
 M1 = 0xCD9E8D57
 B0 = 0x9E3779B9
@@ -128,6 +130,16 @@ def draw_interarrival(key: int, ctr: int, t: float, mode: str, rate: float,
                     ia = w
                     break
     return ia, ctr
+
+
+def draw_profile_gap(key: int, ctr: int, t: float, rate: float, period: float,
+                     m, cum):
+    """Profile-mode inter-arrival -> (ia, counter afterwards): one unit
+    exponential at ``ctr``; an off stream draws nothing."""
+    if not (rate > 0 and cum[len(m)] > 0):
+        return D_INF, ctr
+    E = rexp_map(philox_u01(key, ctr), 1.0)
+    return profile_gap(E, t, rate, period, m, cum), ctr + 1
 
 
 def replica_key(seed: int, global_replica_id: int) -> int:

@@ -40,7 +40,8 @@ from ..utils.logging import LOGGER_NAME
 from ..utils.timers import Lap, ThroughputMeter
 from .oracle import ALGOS
 from .state import (ARR_CAP, INF, LH_BINS, RL_HID, SERIES_METRICS,
-                    alloc_state, engine_cfg, engine_dims, load_tensors)
+                    alloc_state, engine_cfg, engine_dims, load_tensors,
+                    profile_table, validate_profile_engine)
 
 # the fleet row of the population series (per-DC rows: SERIES_METRICS)
 SERIES_FLEET = "ALL"
@@ -99,7 +100,8 @@ def seed_arrivals(n_ing, procs_of_replica, seed, shard):
     matching the device recipe (philox.hpp).  ``procs_of_replica(r)`` is
     local replica r's ``(arrival_inf, arrival_trn)``: one shared pair for a
     uniform engine, the replica's own parameters under a sweep."""
-    from ._philox_host import philox_u01, replica_key, rexp
+    from ._philox_host import (draw_profile_gap, philox_u01, replica_key,
+                               rexp)
     R = shard.count
     NS = n_ing * 2
     out = np.full((R, NS), INF)
@@ -120,6 +122,13 @@ def seed_arrivals(n_ing, procs_of_replica, seed, shard):
                 continue
             if arr.mode == "poisson":
                 out[r, s] = rexp(key, ctr, arr.rate)
+                ctr += 1
+            elif arr.mode == "profile":
+                # one unit exponential at ctr = stream index, inverted
+                # through the stream's own row at t = 0 (D_INF: a row of 0s)
+                out[r, s] = draw_profile_gap(
+                    key, ctr, 0.0, arr.rate, arr.period,
+                    *arr._table(s >> 1))[0]
                 ctr += 1
             else:  # sinusoid thinning at t=0
                 max_rate = arr.rate * (1.0 + abs(arr.amp))
@@ -187,6 +196,12 @@ class BatchedEngine:
                            arrival_trace=arrival_trace,
                            arrival_pregen=bool(arrival_pregen),
                            subwave=subwave)
+        # per-ingress rate profiles (models/arrivals.py): checked here, before
+        # anything touches the GPU
+        profile_on = validate_profile_engine(
+            arrival_inf, arrival_trn, scenario.n_ing, algo=algo,
+            subwave=subwave, arrival_pregen=bool(arrival_pregen),
+            arrival_trace=arrival_trace)
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedEngine requires a ROCm GPU "
                                "(no silent CPU fallback)")
@@ -259,7 +274,8 @@ class BatchedEngine:
             # and stays the independent reference
             arrival_pregen=bool(arrival_pregen) and subwave == 64,
             arr_cap=arr_cap, latency_hist=latency_hist,
-            latency_sla_s=latency_sla_s, sweep=sweep)
+            latency_sla_s=latency_sla_s, sweep=sweep,
+            arrivals=(arrival_inf, arrival_trn))
         self.dims = dims
         if dims.lat_hist:
             lh_bytes = R * n_dc * 2 * (LH_BINS + 1) * 4
@@ -275,7 +291,9 @@ class BatchedEngine:
                 f"{ps_bytes} bytes ({ps_bytes / 2**20:.1f} MiB)")
         sweep_table = sweep.table(shard, self.sweep_base) \
             if sweep is not None else None
-        t = alloc_state(dims, scenario, dev, arrival_trace, sweep_table)
+        t = alloc_state(dims, scenario, dev, arrival_trace, sweep_table,
+                        profile_table(scenario.n_ing, arrival_inf, arrival_trn)
+                        if profile_on else None)
         if not self.trace_mode:
             # seed the initial arrival times on host (one inf + one trn per
             # ingress per replica), Philox-consistent with the device streams:
@@ -580,15 +598,16 @@ class BatchedEngine:
         st = torch.load(path, map_location="cpu", weights_only=False)
         # a sweep's parameters are state: a checkpoint of another sweep (or
         # of other base values) would silently change this engine's points
-        for k in ("sw_arr", "sw_cap"):
+        for k in ("sw_arr", "sw_cap", "arr_prof"):
             if k in self.t and k in st["tensors"] and \
                     tuple(st["tensors"][k].shape) == tuple(self.t[k].shape) \
                     and not torch.equal(st["tensors"][k].to(self.t[k].dtype),
                                         self.t[k].cpu()):
                 raise ValueError(
                     f"checkpoint tensor {k!r} differs from this engine's own "
-                    "sweep: it was saved by an engine with other parameter "
-                    "points")
+                    + ("rate profile" if k == "arr_prof" else
+                       "sweep: it was saved by an engine with other "
+                       "parameter points"))
         load_tensors(self.t, st["tensors"])
         if self._rl_drv is not None:
             self._rl_drv.rl_updates = st.get("rl_updates", 0)

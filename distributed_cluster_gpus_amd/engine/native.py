@@ -9,7 +9,7 @@ engine is the scale path for RL).
 import os
 from typing import Optional
 
-from ..models.arrivals import ArrivalProcess
+from ..models.arrivals import ArrivalProcess, profile_tables
 from ..models.scenario import PAYLOAD_GB, Scenario
 from ..ops import load_des_core
 from .oracle import ALGOS, OracleEngine
@@ -75,6 +75,16 @@ class NativeEngine:
         }
         out_dir = out_dir or os.getcwd()
         os.makedirs(out_dir, exist_ok=True)
+
+        def arr_dict(a):
+            d = {"mode": a.mode, "rate": float(a.rate), "amp": float(a.amp),
+                 "period": float(a.period)}
+            if a.mode == "profile":
+                # one (m, cum) table per ingress (models/arrivals.py)
+                tabs = [profile_tables(row) for row in a.profile_rows(sc.n_ing)]
+                d["profile_m"] = [list(m) for m, _ in tabs]
+                d["profile_cum"] = [list(c) for _, c in tabs]
+            return d
         params = {
             "algo": _ALGO_IDS[algo],
             "duration": float(duration), "log_interval": float(log_interval),
@@ -84,10 +94,8 @@ class NativeEngine:
             "fixed_freq": float(fixed_freq) if fixed_freq else 0.0,
             "cluster_csv": os.path.join(out_dir, "cluster_log.csv"),
             "job_csv": os.path.join(out_dir, "job_log.csv"),
-            "arr_inf": {"mode": arrival_inf.mode, "rate": float(arrival_inf.rate),
-                        "amp": float(arrival_inf.amp), "period": float(arrival_inf.period)},
-            "arr_trn": {"mode": arrival_trn.mode, "rate": float(arrival_trn.rate),
-                        "amp": float(arrival_trn.amp), "period": float(arrival_trn.period)},
+            "arr_inf": arr_dict(arrival_inf),
+            "arr_trn": arr_dict(arrival_trn),
         }
         self._sim = core.DesSim(sc_dict, params)
         self._sim.set_ingress_names(list(sc.ingress_names))

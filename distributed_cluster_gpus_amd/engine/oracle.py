@@ -168,11 +168,12 @@ class OracleEngine:
 
         # seed arrivals: one inference + one training event per ingress, in
         # ingress order, then the first log tick (reference :153-157).
-        for ing_name in scenario.ingress_names:
-            self._schedule(self.now + self.arr_inf.next_interarrival(self.now, self.rng),
-                           "arrival_inf", {"ing": ing_name})
-            self._schedule(self.now + self.arr_trn.next_interarrival(self.now, self.rng),
-                           "arrival_trn", {"ing": ing_name})
+        # (the ingress index selects the row of a per-ingress rate profile)
+        for ing_i, ing_name in enumerate(scenario.ingress_names):
+            self._schedule(self.now + self.arr_inf.next_interarrival(
+                self.now, self.rng, ing_i), "arrival_inf", {"ing": ing_name})
+            self._schedule(self.now + self.arr_trn.next_interarrival(
+                self.now, self.rng, ing_i), "arrival_trn", {"ing": ing_name})
         self._schedule(self.now + self.log_interval, "log", {"interval": self.log_interval})
         if self.use_control_interval and self.power_cap > 0:
             self._schedule(self.now + self.control_interval, "control", {})
@@ -349,7 +350,8 @@ class OracleEngine:
 
         # self-exciting chain: schedule this ingress's next arrival
         arr = self.arr_inf if jtype == "inference" else self.arr_trn
-        self._schedule(self.now + arr.next_interarrival(self.now, self.rng),
+        self._schedule(self.now + arr.next_interarrival(
+            self.now, self.rng, self._ing_idx[ing_name]),
                        "arrival_inf" if jtype == "inference" else "arrival_trn",
                        {"ing": ing_name})
 

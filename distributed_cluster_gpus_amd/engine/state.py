@@ -23,6 +23,11 @@ It is ordinary state: a checkpoint saves and restores it with the rest.
 The latency histograms (``lh_hist``, ``lh_over``; ops/csrc/hip/lat_hist.hpp)
 exist only when asked for (``latency_hist=True``); their presence is what
 selects the recording kernels.  Ordinary state as well.
+
+The rate-profile table (``arr_prof``; ops/csrc/hip/arrival_ring.hpp) exists
+only when a job type's arrival mode is 'profile'; its presence selects the
+PROF arrival-ring generators.  Constant over a run, saved and restored with
+the rest.
 """
 import math
 from dataclasses import dataclass
@@ -37,7 +42,9 @@ ALGO_IDS = {"default_policy": 0, "cap_uniform": 1, "cap_greedy": 2,
             "joint_nf": 3, "bandit": 4, "carbon_cost": 5, "eco_route": 6,
             "debug": 7, "chsac_af": 8}
 ECO_IDS = {"energy": 0, "carbon": 1, "cost": 2}
-MODE_IDS = {"poisson": 0, "sinusoid": 1, "off": 2}
+MODE_IDS = {"poisson": 0, "sinusoid": 1, "off": 2, "profile": 3}
+PROF_SEG = 64      # most segments of a rate profile (PROF_MAX_SEG)
+PROF_W = 2 * PROF_SEG + 2   # f64 per arr_prof row: K, m[64], cum[65] (PROF_W)
 INF = 1e300
 # population-series metrics per DC, in sample-buffer order (PS_K in
 # ops/csrc/hip/pop_series.hpp)
@@ -94,6 +101,7 @@ class EngineDims:
     lat_sla_s: float = 0.5      # ... and the sojourn their SLA-miss count uses
     sweep: bool = False         # parameter sweep (engine/sweep.py): sw_* exist
     sweep_cap: bool = False     # ... and it has a power_cap axis
+    profile: bool = False       # a job type is in 'profile' mode: arr_prof
 
     @property
     def is_rl(self) -> bool:
@@ -129,7 +137,7 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
                 arrival_pregen: bool = True,
                 arr_cap: int = ARR_CAP, latency_hist: bool = False,
                 latency_sla_s: Optional[float] = None,
-                sweep=None) -> EngineDims:
+                sweep=None, arrivals=None) -> EngineDims:
     """``n_rep`` is this rank's replica count; ``serve_device`` /
     ``weights_buffer`` say whether the kernel serves the policy itself and
     whether the flat actor-weights buffer is needed at all (it also feeds the
@@ -138,7 +146,9 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
     trace mode never have one.  ``latency_hist`` asks for the per-replica
     latency histograms; ``latency_sla_s`` (default ``sla_p99_ms / 1000``) is
     the sojourn above which a finish counts as an SLA miss.  ``sweep`` (a
-    ``Sweep``) records that a parameter sweep is on; it needs the ring."""
+    ``Sweep``) records that a parameter sweep is on; it needs the ring.
+    ``arrivals`` (the ``(inference, training)`` pair) records whether a job
+    type is in 'profile' mode, which needs the ring as well."""
     is_rl = algo == "chsac_af"
     n_dc = scenario.n_dc
     end_time, log_interval = float(duration), float(log_interval)
@@ -165,6 +175,12 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
     if sweep is not None and sweep.has_power_cap and algo != "cap_greedy":
         raise ValueError("a power_cap sweep axis needs algo='cap_greedy', "
                          f"got {algo!r}")
+    profile = arrivals is not None and any(
+        a.mode == "profile" for a in arrivals)
+    if profile and not pregen:
+        raise ValueError("arrival mode 'profile' lives in the arrival-ring "
+                         "generator: it needs arrival_pregen, no "
+                         "arrival_trace and an algo other than chsac_af")
     return EngineDims(
         algo=algo, n_rep=int(n_rep), n_dc=n_dc, n_ing=scenario.n_ing,
         n_freq=scenario.n_freq,
@@ -200,17 +216,79 @@ def engine_dims(scenario: Scenario, *, algo: str, n_rep: int,
         lat_sla_s=float(latency_sla_s) if latency_sla_s is not None
         else float(sla_p99_ms) / 1000.0,
         sweep=sweep is not None,
-        sweep_cap=sweep is not None and sweep.has_power_cap)
+        sweep_cap=sweep is not None and sweep.has_power_cap,
+        profile=profile)
+
+
+def validate_profile_engine(arrival_inf, arrival_trn, n_ing, *, algo,
+                            subwave=64, arrival_pregen=True,
+                            arrival_trace=None) -> bool:
+    """Whether a job type is in 'profile' mode; ValueError, with the reason,
+    where such an engine cannot be built.  Plain Python: runs before anything
+    touches a GPU."""
+    from ..models.arrivals import check_profile
+    named = (("inference", arrival_inf), ("training", arrival_trn))
+    on = [(n, a) for n, a in named if a.mode == "profile"]
+    for name, a in on:
+        try:
+            rows = check_profile(a.profile).shape[0]
+        except ValueError as e:
+            raise ValueError(f"{name} arrivals: {e}") from None
+        if rows not in (1, int(n_ing)):
+            raise ValueError(
+                f"{name} arrivals: profile has {rows} rows; it needs 1 "
+                f"(shared) or n_ing = {n_ing}")
+        if not (math.isfinite(a.period) and a.period > 0):
+            raise ValueError(f"{name} arrivals: profile period = {a.period} "
+                             "must be > 0")
+        if not (math.isfinite(a.rate) and a.rate >= 0):
+            raise ValueError(f"{name} arrivals: profile rate = {a.rate} "
+                             "must be finite and >= 0")
+    if not on:
+        return False
+    why = "arrival mode 'profile' lives in the arrival-ring generator"
+    if algo == "chsac_af":
+        raise ValueError(f"{why}; algo='chsac_af' draws its arrivals inside "
+                         "the advance kernel")
+    if int(subwave) != 64:
+        raise ValueError(f"{why}; the 8-lane build (subwave={subwave}) has "
+                         "none")
+    if not arrival_pregen:
+        raise ValueError(f"{why}; arrival_pregen=False draws inside the "
+                         "advance kernel")
+    if arrival_trace is not None:
+        raise ValueError(f"{why}; arrival_trace replays recorded arrivals "
+                         "instead of drawing any")
+    return True
+
+
+def profile_table(n_ing, arrival_inf, arrival_trn) -> np.ndarray:
+    """``arr_prof``: [n_streams, PROF_W] f64, row ``ing * 2 + jtype`` = (K,
+    m[0..K-1] padded to 64, cum[0..K] padded to 65); a job type that is not
+    in profile mode has rows of zeros (K = 0), which nobody reads."""
+    from ..models.arrivals import profile_tables
+    tab = np.zeros((n_ing * 2, PROF_W))
+    for jt, a in enumerate((arrival_inf, arrival_trn)):
+        if a.mode != "profile":
+            continue
+        for i, row in enumerate(a.profile_rows(n_ing)):
+            m, cum = profile_tables(row)
+            K = len(m)
+            tab[i * 2 + jt, 0] = K
+            tab[i * 2 + jt, 1:1 + K] = m
+            tab[i * 2 + jt, 1 + PROF_SEG:2 + PROF_SEG + K] = cum
+    return tab
 
 
 def alloc_state(dims: EngineDims, scenario: Scenario, device,
-                arrival_trace=None, sweep_table=None) -> dict:
+                arrival_trace=None, sweep_table=None, prof_table=None) -> dict:
     """The engine's tensors by EngineDesc field name, in their initial state.
     ``arr_next`` holds the trace's first arrivals in trace mode and +inf
     otherwise (the caller seeds it); ``rng_ctr`` starts past the one counter
     block per stream that seeding consumes.  ``sweep_table`` is the ``(arr,
     cap)`` pair of ``Sweep.table`` for this rank's replicas, required exactly
-    when ``dims.sweep``."""
+    when ``dims.sweep``; ``prof_table`` is ``profile_table``'s, required
+    exactly when ``dims.profile``."""
     d = dims
     dev = torch.device(device)
     R, n_dc, n_freq, NS = d.n_rep, d.n_dc, d.n_freq, d.n_streams
@@ -356,6 +434,17 @@ def alloc_state(dims: EngineDims, scenario: Scenario, device,
                 f"{R} replicas need {(R, 2, 3)} / {(R,)}")
         t["sw_arr"] = T(sw_arr, dtype=torch.float64)
         t["sw_cap"] = T(sw_cap, dtype=torch.float64)
+
+    # per-stream rate profiles (opt-in): read by the PROF arrival-ring
+    # generators, written by nobody on the device
+    if d.profile != (prof_table is not None):
+        raise ValueError("alloc_state: prof_table goes with dims.profile")
+    if d.profile:
+        tab = np.asarray(prof_table, np.float64)
+        if tab.shape != (NS, PROF_W):
+            raise ValueError(f"profile table is {tab.shape}, {NS} streams "
+                             f"need {(NS, PROF_W)}")
+        t["arr_prof"] = T(tab, dtype=torch.float64)
 
     # arrival-trace replay mode (exact single-replica parity testing):
     # arrivals come from a recorded (time, size) FIFO per stream

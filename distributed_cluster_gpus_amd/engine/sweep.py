@@ -212,6 +212,11 @@ class Sweep:
                 raise ValueError(
                     f"sweep: axis {swept[0]} sweeps a job type whose base "
                     "arrival mode is 'off' (modes are not swept)")
+            if mode == "profile" and jt + "_amp" in self.axes:
+                raise ValueError(
+                    f"sweep: axis {jt}_amp sweeps a job type in arrival mode "
+                    "'profile', which has no amplitude (its table sets the "
+                    "shape; sweep the rate or the period)")
         if self.has_power_cap and algo != "cap_greedy":
             raise ValueError(
                 f"sweep: a power_cap axis needs algo='cap_greedy', got "

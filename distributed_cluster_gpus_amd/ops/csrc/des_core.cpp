@@ -54,11 +54,38 @@ static inline double unit_time_s(int n, double f, const double* c) {
 }
 
 // ---------- arrivals ----------
-enum class ArrMode { POISSON, SINUSOID, OFF };
+enum class ArrMode { POISSON, SINUSOID, OFF, PROFILE };
+
+// Exact inversion of a piecewise-constant rate profile: models/arrivals.py
+// profile_gap, operation for operation (this file is built without FMA
+// contraction, so a*b+c rounds twice as it does in Python).  m: K multipliers,
+// cum: K + 1 entries, cum[k] = (m[0] + ... + m[k-1]) / K.
+static inline double profile_gap(double E, double t, double rate,
+                                 double period, const std::vector<double>& m,
+                                 const std::vector<double>& cum) {
+  const int K = (int)m.size();
+  const double M = cum[K];
+  if (!(rate > 0 && M > 0)) return INF;
+  double x = std::fmod(t, period) / period;
+  int k0 = std::min(K - 1, (int)(x * K));
+  double A = cum[k0] + (x - (double)k0 / K) * m[k0];
+  double T = A + E / (rate * period);
+  double n = std::floor(T / M);
+  double Tp = T - n * M;
+  if (Tp >= M) { Tp -= M; n += 1; }
+  if (Tp < 0) Tp = 0.0;
+  int k = K - 1;
+  for (int j = 0; j < K; ++j)
+    if (cum[j + 1] > Tp) { k = j; break; }
+  double xp = (double)k / K + (Tp - cum[k]) / m[k];
+  return std::max(0.0, (n + xp - x) * period);
+}
 
 struct Arrival {
   ArrMode mode;
   double rate, amp, period;
+  // PROFILE: one (m, cum) table per ingress, or a single shared one
+  std::vector<std::vector<double>> prof_m, prof_cum;
 
   double lambda_t(double t) const {
     if (mode == ArrMode::POISSON) return rate;
@@ -67,7 +94,14 @@ struct Arrival {
                       std::fmod(t, period) / period)));
     return 0.0;
   }
-  double next_interarrival(double t, PyRandom& rng) const {
+  double next_interarrival(double t, PyRandom& rng, int ingress = 0) const {
+    if (mode == ArrMode::PROFILE) {
+      size_t row = prof_m.size() == 1 ? 0 : (size_t)ingress;
+      const auto& m = prof_m.at(row);
+      const auto& cum = prof_cum.at(row);
+      if (!(rate > 0 && cum[m.size()] > 0)) return INF;  // off: no draw
+      return profile_gap(rng.expovariate(1.0), t, rate, period, m, cum);
+    }
     if (mode == ArrMode::POISSON)
       return rate <= 0 ? INF : rng.expovariate(rate);
     if (mode == ArrMode::SINUSOID) {
@@ -199,8 +233,8 @@ class DesSim {
 
     // seed arrivals (one inf + one trn per ingress, then first log tick)
     for (int i = 0; i < n_ing_; ++i) {
-      schedule(now_ + arr_[0].next_interarrival(now_, rng_), EV_ARR_INF, i, 0, 0);
-      schedule(now_ + arr_[1].next_interarrival(now_, rng_), EV_ARR_TRN, i, 0, 0);
+      schedule(now_ + arr_[0].next_interarrival(now_, rng_, i), EV_ARR_INF, i, 0, 0);
+      schedule(now_ + arr_[1].next_interarrival(now_, rng_, i), EV_ARR_TRN, i, 0, 0);
     }
     schedule(now_ + log_interval_, EV_LOG, 0, 0, 0);
 
@@ -323,7 +357,17 @@ class DesSim {
     Arrival a;
     std::string m = d["mode"].cast<std::string>();
     a.mode = m == "poisson" ? ArrMode::POISSON
-             : (m == "sinusoid" ? ArrMode::SINUSOID : ArrMode::OFF);
+             : (m == "sinusoid" ? ArrMode::SINUSOID
+             : (m == "profile" ? ArrMode::PROFILE : ArrMode::OFF));
+    if (a.mode == ArrMode::PROFILE) {
+      a.prof_m = d["profile_m"].cast<std::vector<std::vector<double>>>();
+      a.prof_cum = d["profile_cum"].cast<std::vector<std::vector<double>>>();
+      if (a.prof_m.empty() || a.prof_m.size() != a.prof_cum.size())
+        throw std::invalid_argument("profile mode needs profile_m / profile_cum");
+      for (size_t r = 0; r < a.prof_m.size(); ++r)
+        if (a.prof_m[r].empty() || a.prof_cum[r].size() != a.prof_m[r].size() + 1)
+          throw std::invalid_argument("profile row: cum needs K + 1 entries");
+    }
     a.rate = d["rate"].cast<double>();
     a.amp = d["amp"].cast<double>();
     a.period = d["period"].cast<double>();
@@ -475,7 +519,7 @@ class DesSim {
     jobs_.emplace(jid, job);
     schedule(now_ + transfer_s, EV_XFER, 0, jid, 0);
 
-    double ia = arr_[jtype].next_interarrival(now_, rng_);
+    double ia = arr_[jtype].next_interarrival(now_, rng_, ing);
     schedule(now_ + ia, jtype == 0 ? EV_ARR_INF : EV_ARR_TRN, ing, 0, 0);
   }
 

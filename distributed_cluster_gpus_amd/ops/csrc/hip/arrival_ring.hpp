@@ -77,6 +77,50 @@ __device__ __forceinline__ int pg_group_ballot(bool p, int lane64) {
   return (int)((m >> (lane64 & ~(PG_GROUP - 1))) & 0xffull);
 }
 
+// Arrival mode 3, a piecewise-constant rate profile (ProfDesc): the gap g >= 0
+// after an arrival at t with integral_t^{t+g} lambda = E, E a unit
+// exponential, by exact inversion; no thinning.  models/arrivals.py
+// profile_gap is the host twin, operation for operation: contraction is off,
+// so a*b+c rounds twice here as it does there, and fmod, the division and
+// floor are exact or correctly rounded on both sides.  Called by all eight
+// lanes of a group with the same arguments; the lanes share the search for
+// the landing segment (lane gl tests segments gl, gl + 8, ..., the group
+// ballot picks the first), and all return the same value.  D_INF where the
+// stream is off (rate 0 or a row of zeros); the caller then draws nothing.
+__device__ __forceinline__ bool profile_on(double rate, const double* row) {
+  const int K = min((int)row[0], PROF_MAX_SEG);
+  return rate > 0 && row[1 + PROF_MAX_SEG + K] > 0;
+}
+__device__ __forceinline__ double profile_gap(double E, double t, double rate,
+                                              double period, const double* row,
+                                              int gl, int lane64) {
+#pragma clang fp contract(off)
+  const int K = min((int)row[0], PROF_MAX_SEG);
+  const double* m = row + 1;
+  const double* cum = row + 1 + PROF_MAX_SEG;
+  const double M = cum[K];
+  if (!(rate > 0 && M > 0)) return D_INF;
+  const double x = fmod(t, period) / period;
+  const int k0 = min(K - 1, (int)(x * (double)K));
+  const double A = cum[k0] + (x - (double)k0 / (double)K) * m[k0];
+  const double T = A + E / (rate * period);
+  double n = floor(T / M);
+  double Tp = T - n * M;
+  if (Tp >= M) { Tp -= M; n += 1.0; }
+  if (Tp < 0) Tp = 0.0;
+  // the first k with cum[k + 1] > Tp: cum[k] <= Tp, hence m[k] > 0
+  int k = K - 1;
+  bool found = false;
+  for (int j = 0; j < K && !found; j += PG_GROUP) {
+    const int kk = j + gl;
+    const bool p = kk < K && cum[kk + 1] > Tp;
+    const int b = pg_group_ballot(p, lane64);
+    if (b) { k = j + __ffs(b) - 1; found = true; }
+  }
+  const double xp = (double)k / (double)K + (Tp - cum[k]) / m[k];
+  return fmax(0.0, (n + xp - x) * period);
+}
+
 // Tops every live replica's ring up to ring_topup_target(budget, cap)
 // records, or to the last arrival not later than min(end_time, t_target),
 // whichever comes first, continuing from the generator's frontier.  With an
@@ -87,10 +131,14 @@ __device__ __forceinline__ int pg_group_ballot(bool p, int lane64) {
 // SWP: a parameter sweep is on (SweepDesc): rate, amplitude and period are
 // the replica's own, loaded once per lane before the walk, instead of the
 // EngineDesc scalars.  The modes are not swept.  SWP = false never looks at W.
-template <bool SWP>
+//
+// PROF: a job type is in mode 3 (rate profile): its gap is one draw inverted
+// through the winning stream's row of P (profile_gap).  The other job type
+// keeps its own mode.  PROF = false never looks at P and holds no code for it.
+template <bool SWP, bool PROF>
 __global__ void __launch_bounds__(PG_THREADS)
 pregen_arrivals_kernel(EngineDesc S, ArrRing A, double t_target,
-                       long long budget, SweepDesc W) {
+                       long long budget, SweepDesc W, ProfDesc P) {
   const int r = (int)((blockIdx.x * (unsigned)PG_THREADS + threadIdx.x) /
                       PG_GROUP);
   const int gl = threadIdx.x & (PG_GROUP - 1);
@@ -189,7 +237,23 @@ pregen_arrivals_kernel(EngineDesc S, ArrRing A, double t_target,
                                 : (jt ? S.arr_period[1] : S.arr_period[0]);
       const double lambd = mode == 1 ? rate * (1.0 + fabs(amp)) : rate;
       double ia = D_INF;
-      if ((mode == 0 || mode == 1) && lambd > 0) {
+      bool prof = false;
+      if constexpr (PROF) {
+        prof = mode == 3;
+        if (prof) {
+          // one draw, the same in every lane, as in the Poisson case; rows
+          // differ between the groups of a wave, a group reads one
+          const double* row = P.tab + (int64_t)bi * PROF_W;
+          if (profile_on(rate, row)) {
+            uint32_t w[4];
+            philox4x32(key, c, w);
+            const double E = rexp_map(u01_map(w[0], w[1]), 1.0);
+            ia = profile_gap(E, bv, rate, period, row, gl, lane64);
+            c += 1;
+          }
+        }
+      }
+      if (!prof && (mode == 0 || mode == 1) && lambd > 0) {
         // Poisson: one draw, the same in every lane.  Sinusoid: lane pair
         // (2i, 2i+1) is round i of this pass, up to 4096 rounds in all
         for (int pass = 0; pass < 4096 / (PG_GROUP / 2); ++pass) {

@@ -420,7 +420,72 @@ torch::Tensor energy_freq_debug(torch::Tensor pc, torch::Tensor lc,
   return f;
 }
 
+#if DCG_SUBWAVE == 64
+// standalone driver for the rate-profile inversion (arrival_ring.hpp): one
+// 8-lane group per row runs the production profile_gap on (E, t) through the
+// row's stream of the table, as the generator's groups do
+__global__ void __launch_bounds__(PG_THREADS)
+profile_gap_debug_kernel(const double* E, const double* t, const int* stream,
+                         int64_t B, double rate, double period,
+                         const double* tab, double* out) {
+  const int64_t row = ((int64_t)blockIdx.x * PG_THREADS + threadIdx.x) /
+                      PG_GROUP;
+  const int gl = threadIdx.x & (PG_GROUP - 1);
+  const int lane64 = threadIdx.x & 63;
+  if (row >= B) return;  // whole groups leave together
+  const double g = profile_gap(E[row], t[row], rate, period,
+                               tab + (int64_t)stream[row] * PROF_W, gl,
+                               lane64);
+  if (gl == 0) out[row] = g;
+}
+
+torch::Tensor profile_gap_debug(torch::Tensor E, torch::Tensor t,
+                                torch::Tensor stream, double rate,
+                                double period, torch::Tensor tab) {
+  TORCH_CHECK(E.is_cuda() && t.is_cuda() && stream.is_cuda() &&
+              tab.is_cuda() && E.dtype() == torch::kFloat64 &&
+              t.dtype() == torch::kFloat64 &&
+              stream.dtype() == torch::kInt32 &&
+              tab.dtype() == torch::kFloat64);
+  TORCH_CHECK(E.dim() == 1 && t.sizes() == E.sizes() &&
+              stream.sizes() == E.sizes());
+  TORCH_CHECK(tab.dim() == 2 && tab.size(1) == PROF_W && tab.size(0) >= 1,
+              "tab must be [n_streams][", PROF_W, "]");
+  E = E.contiguous();
+  t = t.contiguous();
+  stream = stream.contiguous();
+  tab = tab.contiguous();
+  int64_t B = E.size(0);
+  auto out = torch::empty({B}, E.options());
+  if (B == 0) return out;
+  TORCH_CHECK(B < (1 << 24));
+  TORCH_CHECK((stream >= 0).all().item<bool>() &&
+                  (stream < tab.size(0)).all().item<bool>(),
+              "stream outside [0, n_streams)");
+  auto Kcol = tab.select(1, 0);
+  TORCH_CHECK((Kcol >= 0).all().item<bool>() &&
+                  (Kcol <= PROF_MAX_SEG).all().item<bool>(),
+              "K outside [0, ", PROF_MAX_SEG, "]");
+  hipStream_t hs = at::hip::getCurrentHIPStream();
+  const int64_t per_block = PG_THREADS / PG_GROUP;
+  hipLaunchKernelGGL(profile_gap_debug_kernel,
+                     dim3((unsigned)((B + per_block - 1) / per_block)),
+                     dim3(PG_THREADS), 0, hs, E.data_ptr<double>(),
+                     t.data_ptr<double>(), stream.data_ptr<int>(), B, rate,
+                     period, tab.data_ptr<double>(), out.data_ptr<double>());
+  check_launch("profile_gap_debug_kernel");
+  return out;
+}
+#endif  // DCG_SUBWAVE == 64
+
 inline void bind_debug_entries(py::module_& m) {
+#if DCG_SUBWAVE == 64
+  m.def("profile_gap_debug", &dcg::profile_gap_debug,
+        "production profile_gap, one 8-lane group per row of (E[B] f64, "
+        "t[B] f64, stream[B] i32) through tab[n_streams, PROF_W] -> gap[B]",
+        py::arg("E"), py::arg("t"), py::arg("stream"), py::arg("rate"),
+        py::arg("period"), py::arg("tab"));
+#endif
   m.def("rl_forward_debug", &dcg::rl_forward_debug,
         "batched actor forward via the in-kernel serving math "
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",

@@ -100,7 +100,8 @@ struct EngineDesc {
                                   //   energy-freq argmins; times stay f64)
   double fixed_freq;
   double payload_gb[2];
-  // arrival processes by jtype: mode 0=poisson 1=sinusoid 2=off
+  // arrival processes by jtype: mode 0=poisson 1=sinusoid 2=off 3=profile
+  // (profile: the arrival-ring generator's only, with ProfDesc below)
   int arr_mode[2];
   double arr_rate[2], arr_amp[2], arr_period[2];
   uint64_t seed;
@@ -292,6 +293,25 @@ struct ArrRing {
 struct SweepDesc {
   const double* arr;              // [r][2][3] (jtype; rate, amp, period)
   const double* cap;              // [r] power cap; null: no power_cap axis
+};
+
+// Per-stream rate profiles (arrival mode 3; models/arrivals.py): stream s =
+// ing * 2 + jtype runs at rate * m[floor(K * frac(t / period))], rate and
+// period being the job type's (EngineDesc, or the replica's own under a
+// sweep).  One row of PROF_W doubles per stream:
+//   [0]        K, the number of segments (1..PROF_MAX_SEG; 0 in the rows of
+//              a job type that is not in profile mode, which nobody reads)
+//   [1..64]    m[0..K-1], the multipliers (>= 0), zero-padded
+//   [65..129]  cum[0..K], cum[k] = (m[0] + ... + m[k-1]) / K, zero-padded
+// m and cum are contiguous so that the eight lanes of a generator group read
+// eight adjacent cum entries per step of the segment search.  Read by
+// pregen_arrivals_kernel<*, true> only and written by nobody on the device;
+// a trailing argument of the GENERATOR alone, so that neither EngineDesc nor
+// ArrRing, which the advance kernels take, changes.  null: off.
+constexpr int PROF_MAX_SEG = 64;
+constexpr int PROF_W = 2 * PROF_MAX_SEG + 2;
+struct ProfDesc {
+  const double* tab;              // [n_streams][PROF_W]
 };
 
 // the Python side allocates the records as float64 rows (s_rec [.., 8],

@@ -2433,6 +2433,29 @@ class BatchedSimHip {
       if (cap_axis) bind(sw_.cap, "sw_cap", R);
       else bind.unused("sw_cap");
     }
+    // rate profiles (arrival mode 3): the table is the generator's, bound
+    // exactly where a job type is in that mode
+    const bool prof_mode = S_.arr_mode[0] == 3 || S_.arr_mode[1] == 3;
+    if (prof_mode || t_.count("arr_prof") != 0) {
+      if (!prof_mode)
+        throw std::invalid_argument(
+            "engine tensor 'arr_prof': no job type is in arrival mode 3 "
+            "(profile), required no such tensor");
+      if (ar_.cap == 0)
+        throw std::invalid_argument(
+            "engine tensor 'arr_prof': arrival mode 3 (profile) lives in the "
+            "arrival-ring generator, required arr_cap > 0 in the 64-lane "
+            "build");
+      auto it = t_.find("arr_prof");
+      if (it != t_.end() &&
+          (it->second.dim() != 2 || it->second.size(1) != PROF_W))
+        throw std::invalid_argument(
+            "engine tensor 'arr_prof': required rows of " +
+            std::to_string(PROF_W) + " (K, m[64], cum[65]), found " +
+            std::to_string(it->second.dim()) + " dims, last of " +
+            std::to_string(it->second.dim() ? it->second.size(-1) : 0));
+      bind(pf_.tab, "arr_prof", NS * PROF_W);
+    }
     contract_ = bind.rows();
     on_gpu_ = bind.on_gpu();
     device_ = bind.device_str();
@@ -2589,11 +2612,14 @@ class BatchedSimHip {
         // same stream, so the ring is topped up before the windows read it
         const int per_block = PG_THREADS / PG_GROUP;
         // a sweep's generator reads the replica's own arrival parameters
-        auto gen = sw_.arr ? pregen_arrivals_kernel<true>
-                           : pregen_arrivals_kernel<false>;
+        // and a rate profile's the per-stream table
+        auto gen = pf_.tab ? (sw_.arr ? pregen_arrivals_kernel<true, true>
+                                      : pregen_arrivals_kernel<false, true>)
+                           : (sw_.arr ? pregen_arrivals_kernel<true, false>
+                                      : pregen_arrivals_kernel<false, false>);
         hipLaunchKernelGGL(gen, dim3((S_.n_rep + per_block - 1) / per_block),
                            dim3(PG_THREADS), 0, stream(), S_, ar_, t_target,
-                           ev, sw_);
+                           ev, sw_, pf_);
         check_launch("pregen_arrivals_kernel launch failed");
       }
 #endif
@@ -2718,6 +2744,7 @@ class BatchedSimHip {
   ArrRing ar_{};                  // cap == 0: arrivals drawn in the kernel
   LatHistDesc lh_{};              // hist == nullptr: feature off
   SweepDesc sw_{};                // arr == nullptr: no parameter sweep
+  ProfDesc pf_{};                 // tab == nullptr: no rate profile
   // launch plan (launch_plan.hpp)
   int forced_capacity_ = 0;       // 0: the runtime's occupancy answer
   int queried_capacity_ = 0;      // cache of that answer

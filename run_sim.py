@@ -13,6 +13,11 @@ Extensions over the reference:
                                      ensemble (batched engine)
   --latency-hist                     latency tail quantiles and SLA misses
                                      over the replica ensemble (batched engine)
+  --inf-mode profile / --trn-mode profile
+                                     per-ingress piecewise-constant arrival
+                                     rates (--inf-profile / --trn-profile FILE,
+                                     or --ingress-tz-offsets-h for a sinusoid
+                                     shifted per ingress), every engine
   --sweep-inf-rate / --sweep-trn-rate / --sweep-power-cap A,B,..
                                      a grid of parameter points inside one
                                      replica ensemble (batched engine)
@@ -45,15 +50,33 @@ def parse_args(argv=None):
 
     # --- arrivals (inference) ---
     p.add_argument("--inf-mode", type=str, default="sinusoid",
-                   choices=["poisson", "sinusoid", "off"])
+                   choices=["poisson", "sinusoid", "off", "profile"])
     p.add_argument("--inf-rate", type=float, default=6.0)
     p.add_argument("--inf-amp", type=float, default=0.6)
     p.add_argument("--inf-period", type=float, default=300.0)
 
     # --- arrivals (training) ---
     p.add_argument("--trn-mode", type=str, default="poisson",
-                   choices=["poisson", "sinusoid", "off"])
+                   choices=["poisson", "sinusoid", "off", "profile"])
     p.add_argument("--trn-rate", type=float, default=0.3)
+    p.add_argument("--trn-period", type=float, default=3600.0,
+                   help="Cycle of a training rate profile (seconds).")
+
+    # --- per-ingress rate profiles (mode 'profile') ---
+    for kind in ("inf", "trn"):
+        p.add_argument(f"--{kind}-profile", type=str, default=None,
+                       metavar="FILE",
+                       help=f"--{kind}-mode profile: CSV of n_ing rows (or one "
+                            "shared row) x K <= 64 columns of rate "
+                            f"multipliers; --{kind}-rate scales them and "
+                            f"--{kind}-period is the cycle.")
+    p.add_argument("--ingress-tz-offsets-h", type=_float_list, default=None,
+                   metavar="H0,H1,..",
+                   help="--inf-mode profile without --inf-profile: one "
+                        "time-zone offset in hours per ingress; the table is "
+                        "the --inf-rate/--inf-amp/--inf-period sinusoid in 24 "
+                        "segments, shifted per ingress by H/24 of the period "
+                        "(the period stands for one day).")
 
     # --- algorithm / controller ---
     p.add_argument("--algo", type=str, default="default_policy",
@@ -158,6 +181,29 @@ def sweep_axes(args):
     return {name: vals for name, vals in given if vals is not None}
 
 
+def profile_arrival(kind, mode, rate, amp, period, path, offsets_h, n_ing):
+    """The ArrivalProcess of one job type from the CLI flags: the plain modes
+    as before; 'profile' from its CSV file, or (inference) from the per-ingress
+    time-zone offsets."""
+    from distributed_cluster_gpus_amd.models.arrivals import ArrivalProcess
+    if mode != "profile":
+        return ArrivalProcess(mode=mode, rate=rate, amp=amp, period=period)
+    if kind == "trn" and not path:
+        raise SystemExit("--trn-mode profile needs --trn-profile FILE")
+    if path:
+        ap = ArrivalProcess.from_csv(path, rate=rate, period=period, amp=amp)
+    elif kind == "inf" and offsets_h:
+        ap = ArrivalProcess.diurnal(
+            rate, amp, period, [h / 24.0 * period for h in offsets_h],
+            segments=24)
+    else:
+        raise SystemExit(f"--{kind}-mode profile needs --{kind}-profile FILE"
+                         + (" or --ingress-tz-offsets-h" if kind == "inf"
+                            else ""))
+    ap.profile_rows(n_ing)        # 1 or n_ing rows, or ValueError
+    return ap
+
+
 def resolve_out_dir(log_path, algo):
     """Reference output-dir rule (run_sim_paper.py:136-140): a bare name gets
     the algo appended; a path containing a separator is used as-is."""
@@ -183,9 +229,22 @@ def main(argv=None):
     for m in warnings:
         print("[GPU VALIDATION]", m)
 
+    # (a 'profile' type is built below, from its table)
+    plain = {"profile": "off"}
     arrival_inf, arrival_trn = build_arrivals(
-        inf_mode=args.inf_mode, inf_rate=args.inf_rate, inf_amp=args.inf_amp,
-        inf_period=args.inf_period, trn_mode=args.trn_mode, trn_rate=args.trn_rate)
+        inf_mode=plain.get(args.inf_mode, args.inf_mode),
+        inf_rate=args.inf_rate, inf_amp=args.inf_amp,
+        inf_period=args.inf_period,
+        trn_mode=plain.get(args.trn_mode, args.trn_mode),
+        trn_rate=args.trn_rate)
+    if "profile" in (args.inf_mode, args.trn_mode):
+        arrival_inf = profile_arrival(
+            "inf", args.inf_mode, args.inf_rate, args.inf_amp, args.inf_period,
+            args.inf_profile, args.ingress_tz_offsets_h, sc.n_ing)
+        arrival_trn = profile_arrival(
+            "trn", args.trn_mode, args.trn_rate, arrival_trn.amp,
+            args.trn_period if args.trn_mode == "profile"
+            else arrival_trn.period, args.trn_profile, None, sc.n_ing)
     sc.arrival_inf, sc.arrival_trn = arrival_inf, arrival_trn
 
     out_dir = resolve_out_dir(args.log_path, args.algo)

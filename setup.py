@@ -17,7 +17,10 @@ ext = Extension(
     sources=["distributed_cluster_gpus_amd/ops/csrc/des_core.cpp"],
     include_dirs=[pybind11.get_include()],
     language="c++",
-    extra_compile_args=["-O3", "-std=c++17", "-fvisibility=hidden"],
+    # no FMA contraction: the core's floating-point expressions must round
+    # like Python's, operation by operation, on every target
+    extra_compile_args=["-O3", "-std=c++17", "-fvisibility=hidden",
+                        "-ffp-contract=off"],
 )
 
 setup(
