@@ -7,7 +7,7 @@ a population report: mean / std / standard error / percentiles / confidence
 intervals for energy, completed jobs and latency — the capability SURVEY §6
 names as the rebuild's north star.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -93,17 +93,108 @@ def population_report(engine, out_dir: Optional[str] = None,
 # (BatchedEngine(pop_series=True); reduced on the GPU by ops reduce_series)
 # ---------------------------------------------------------------------------
 @dataclass
-class SeriesStats:
-    """Per-tick ensemble statistics.  ``time`` is [T]; ``n``, ``mean``,
-    ``m2`` (sum of squared deviations from the mean), ``min`` and ``max`` are
-    [T, len(dc_names), len(metrics)].  The last entry of ``dc_names`` is the
-    fleet row.  Cells with n == 0 hold NaN mean/min/max and m2 == 0."""
-    time: np.ndarray
+class Moments:
+    """{n, mean, M2, min, max} of a per-replica figure over a replica
+    ensemble, per cell: ``n`` (int64), ``mean``, ``m2`` (sum of squared
+    deviations from the mean), ``min`` and ``max`` share one shape.  Cells
+    with n == 0 hold NaN mean/min/max and m2 == 0."""
     n: np.ndarray
     mean: np.ndarray
     m2: np.ndarray
     min: np.ndarray
     max: np.ndarray
+
+    @classmethod
+    def from_array(cls, a, **own):
+        """a: [..., 5] = {n, mean, M2, min, max}; ``own``: the fields a
+        subclass adds."""
+        a = np.asarray(a, dtype=np.float64)
+        return cls(a[..., 0].astype(np.int64), a[..., 1].copy(),
+                   a[..., 2].copy(), a[..., 3].copy(), a[..., 4].copy(),
+                   **own)
+
+    def to_array(self) -> np.ndarray:
+        """Inverse of from_array: [..., 5] float64."""
+        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
+                         self.min, self.max], axis=-1)
+
+    @classmethod
+    def from_values(cls, values, slices, **own):
+        """values: [R, K] per-replica figures; slices: one ``(a, b)`` replica
+        range per group (empty where this rank holds none of it).  Two-pass,
+        shifted by the mean: sum of (x - mean)^2.  NaN figures are skipped."""
+        v = np.asarray(values, dtype=np.float64)
+        G, K = len(slices), v.shape[1]
+        n = np.zeros((G, K), np.int64)
+        mean, lo, hi = (np.full((G, K), np.nan) for _ in range(3))
+        m2 = np.zeros((G, K))
+        for g, (a, b) in enumerate(slices):
+            for k in range(K):
+                x = v[a:b, k]
+                x = x[~np.isnan(x)]
+                if x.size == 0:
+                    continue
+                mu = x.sum() / x.size
+                d = x - mu
+                n[g, k], mean[g, k] = x.size, mu
+                m2[g, k] = (d * d).sum()
+                lo[g, k], hi[g, k] = x.min(), x.max()
+        return cls(n, mean, m2, lo, hi, **own)
+
+    def merge(self, b, **own):
+        """Statistics of the union of two disjoint replica groups: Chan et
+        al. parallel combination of (n, mean, M2) per cell, min and max
+        directly.  An empty side contributes nothing (its NaN mean never
+        enters the arithmetic).  The other fields are ``self``'s, or
+        ``own``'s."""
+        a = self
+        na, nb = a.n.astype(np.float64), b.n.astype(np.float64)
+        n = na + nb
+        ea, eb = a.n == 0, b.n == 0
+        ma, mb = np.where(ea, 0.0, a.mean), np.where(eb, 0.0, b.mean)
+        delta = mb - ma
+        safe_n = np.where(n > 0, n, 1.0)
+        mean = ma + delta * (nb / safe_n)
+        m2 = a.m2 + b.m2 + delta * delta * (na * nb / safe_n)
+        return replace(
+            a, n=a.n + b.n,
+            mean=np.where(ea, b.mean, np.where(eb, a.mean, mean)),
+            m2=np.where(ea, b.m2, np.where(eb, a.m2, m2)),
+            min=np.fmin(a.min, b.min), max=np.fmax(a.max, b.max), **own)
+
+    def std(self) -> np.ndarray:
+        """Sample standard deviation (ddof=1); 0 where n < 2."""
+        multi = self.n > 1
+        return np.where(multi, np.sqrt(np.maximum(self.m2, 0.0)
+                                       / np.where(multi, self.n - 1, 1)), 0.0)
+
+    def stderr(self) -> np.ndarray:
+        """Standard error of the mean; 0 where n < 2."""
+        multi = self.n > 1
+        return np.where(multi, self.std()
+                        / np.sqrt(np.where(multi, self.n, 1)), 0.0)
+
+
+def _tree_merge(parts, cls, name: str):
+    """Pairwise (tree-order) ``merge`` of a non-empty sequence."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError(f"{name} needs at least one {cls.__name__}")
+    while len(parts) > 1:
+        nxt = [parts[i].merge(parts[i + 1])
+               for i in range(0, len(parts) - 1, 2)]
+        if len(parts) % 2:
+            nxt.append(parts[-1])
+        parts = nxt
+    return parts[0]
+
+
+@dataclass
+class SeriesStats(Moments):
+    """Per-tick ensemble statistics.  ``time`` is [T]; the moments are
+    [T, len(dc_names), len(metrics)].  The last entry of ``dc_names`` is the
+    fleet row."""
+    time: np.ndarray
     metrics: List[str]
     dc_names: List[str]
 
@@ -111,91 +202,52 @@ class SeriesStats:
     def from_tensor(cls, stats, time, metrics, dc_names) -> "SeriesStats":
         """stats: [T, n_row, K, 5] = {n, mean, M2, min, max} (tensor or array,
         on the host), time: [T]."""
-        a = np.asarray(stats, dtype=np.float64)
-        return cls(time=np.asarray(time, dtype=np.float64).copy(),
-                   n=a[..., 0].astype(np.int64), mean=a[..., 1].copy(),
-                   m2=a[..., 2].copy(), min=a[..., 3].copy(),
-                   max=a[..., 4].copy(), metrics=list(metrics),
-                   dc_names=list(dc_names))
+        return cls.from_array(
+            stats, time=np.asarray(time, dtype=np.float64).copy(),
+            metrics=list(metrics), dc_names=list(dc_names))
 
-    def to_array(self) -> np.ndarray:
-        """Inverse of from_tensor: [T, n_row, K, 5] float64."""
-        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
-                         self.min, self.max], axis=-1)
+    def _reached(self) -> np.ndarray:
+        """[T] bool: the ticks at least one replica has reached."""
+        T = len(self.time)
+        return self.n.reshape(T, -1).max(axis=1) > 0 if self.n.size \
+            else np.zeros(T, bool)
 
     def trimmed(self) -> "SeriesStats":
         """Drop the ticks no replica has reached."""
-        keep = self.n.reshape(len(self.time), -1).max(axis=1) > 0 \
-            if self.n.size else np.zeros(len(self.time), bool)
-        return SeriesStats(self.time[keep], self.n[keep], self.mean[keep],
-                           self.m2[keep], self.min[keep], self.max[keep],
-                           self.metrics, self.dc_names)
+        keep = self._reached()
+        return replace(self, time=self.time[keep], n=self.n[keep],
+                       mean=self.mean[keep], m2=self.m2[keep],
+                       min=self.min[keep], max=self.max[keep])
 
+    def _padded(self, T: int) -> "SeriesStats":
+        """Extend to T ticks with empty cells (n = 0)."""
+        extra = T - len(self.time)
+        if extra <= 0:
+            return self
+        shape = (extra,) + self.n.shape[1:]
+        nan = np.full(shape, np.nan)
+        return replace(
+            self, time=np.concatenate([self.time, np.full(extra, np.nan)]),
+            n=np.concatenate([self.n, np.zeros(shape, np.int64)]),
+            mean=np.concatenate([self.mean, nan]),
+            m2=np.concatenate([self.m2, np.zeros(shape)]),
+            min=np.concatenate([self.min, nan]),
+            max=np.concatenate([self.max, nan]))
 
-def _pad_ticks(s: SeriesStats, T: int) -> SeriesStats:
-    """Extend to T ticks with empty cells (n = 0)."""
-    extra = T - len(s.time)
-    if extra <= 0:
-        return s
-    shape = (extra,) + s.n.shape[1:]
-    nan = np.full(shape, np.nan)
-    return SeriesStats(
-        np.concatenate([s.time, np.full(extra, np.nan)]),
-        np.concatenate([s.n, np.zeros(shape, np.int64)]),
-        np.concatenate([s.mean, nan]), np.concatenate([s.m2, np.zeros(shape)]),
-        np.concatenate([s.min, nan]), np.concatenate([s.max, nan]),
-        s.metrics, s.dc_names)
-
-
-def _chan(a, b):
-    """(mean, m2) of the union of two groups with fields n / mean / m2 of
-    equal shape, per cell."""
-    na, nb = a.n.astype(np.float64), b.n.astype(np.float64)
-    n = na + nb
-    ea, eb = a.n == 0, b.n == 0
-    ma, mb = np.where(ea, 0.0, a.mean), np.where(eb, 0.0, b.mean)
-    delta = mb - ma
-    safe_n = np.where(n > 0, n, 1.0)
-    mean = ma + delta * (nb / safe_n)
-    m2 = a.m2 + b.m2 + delta * delta * (na * nb / safe_n)
-    mean = np.where(ea, b.mean, np.where(eb, a.mean, mean))
-    m2 = np.where(ea, b.m2, np.where(eb, a.m2, m2))
-    return mean, m2
-
-
-def _merge_pair(a: SeriesStats, b: SeriesStats) -> SeriesStats:
-    """Chan et al. parallel combination of (n, mean, M2) per cell; an empty
-    side contributes nothing (its NaN mean never enters the arithmetic)."""
-    assert a.metrics == b.metrics and a.dc_names == b.dc_names
-    T = max(len(a.time), len(b.time))
-    a, b = _pad_ticks(a, T), _pad_ticks(b, T)
-    mean, m2 = _chan(a, b)
-    # a tick's time comes from whichever side has reached it
-    a_has = (a.n.reshape(T, -1).max(axis=1) > 0) if a.n.size \
-        else np.zeros(T, bool)
-    return SeriesStats(np.where(a_has, a.time, b.time), a.n + b.n, mean, m2,
-                       np.fmin(a.min, b.min), np.fmax(a.max, b.max),
-                       a.metrics, a.dc_names)
+    def merge(self, b: "SeriesStats") -> "SeriesStats":
+        assert self.metrics == b.metrics and self.dc_names == b.dc_names
+        T = max(len(self.time), len(b.time))
+        a, b = self._padded(T), b._padded(T)
+        # a tick's time comes from whichever side has reached it
+        return Moments.merge(a, b,
+                             time=np.where(a._reached(), a.time, b.time))
 
 
 def merge_series_stats(parts: Sequence[SeriesStats]) -> SeriesStats:
     """Combine the statistics of disjoint replica groups (shards, ranks,
-    separate runs) into those of their union: pairwise (tree-order) Chan
-    merge of n / mean / M2, min and max merged directly."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_series_stats needs at least one SeriesStats")
-    return _tree_merge(parts, _merge_pair)
-
-
-def _tree_merge(parts: list, pair):
-    while len(parts) > 1:
-        nxt = [pair(parts[i], parts[i + 1])
-               for i in range(0, len(parts) - 1, 2)]
-        if len(parts) % 2:
-            nxt.append(parts[-1])
-        parts = nxt
-    return parts[0]
+    separate runs) into those of their union: pairwise (tree-order)
+    ``Moments.merge``."""
+    return _tree_merge(parts, SeriesStats, "merge_series_stats")
 
 
 SERIES_COLUMNS = ["time_s", "dc", "metric", "n", "mean", "std", "stderr",
@@ -210,10 +262,7 @@ def series_frame(stats: SeriesStats, confidence: float = 0.95) -> pd.DataFrame:
     T, D, K = len(stats.time), len(stats.dc_names), len(stats.metrics)
     n = stats.n.reshape(-1)
     mean = stats.mean.reshape(-1)
-    multi = n > 1
-    std = np.where(multi, np.sqrt(np.maximum(stats.m2.reshape(-1), 0.0)
-                                  / np.where(multi, n - 1, 1)), 0.0)
-    se = np.where(multi, std / np.sqrt(np.where(multi, n, 1)), 0.0)
+    std, se = stats.std().reshape(-1), stats.stderr().reshape(-1)
     return pd.DataFrame({
         "time_s": np.repeat(stats.time, D * K),
         "dc": np.tile(np.repeat(np.asarray(stats.dc_names, object), K), T),
@@ -311,21 +360,15 @@ def quantile_label(q: float) -> str:
 
 
 @dataclass
-class LatencyStats:
+class LatencyStats(Moments):
     """Latency distribution over the replica ensemble.  ``pop_hist`` is
     [len(dc_names), 2, 256] int64, the histogram pooled over the replicas;
-    ``n``, ``mean``, ``m2``, ``min`` and ``max`` are [len(dc_names), 2,
-    len(metrics)]: statistics of each per-replica figure over the replicas
-    that have one (a replica with no finished job in a cell has no quantile
-    and no SLA-miss fraction there).  ``metrics`` is one label per quantile,
-    then ``sla_miss_frac`` and ``jobs``.  The last entry of ``dc_names`` is
-    the fleet row."""
+    the moments are [len(dc_names), 2, len(metrics)]: statistics of each
+    per-replica figure over the replicas that have one (a replica with no
+    finished job in a cell has no quantile and no SLA-miss fraction there).
+    ``metrics`` is one label per quantile, then ``sla_miss_frac`` and
+    ``jobs``.  The last entry of ``dc_names`` is the fleet row."""
     pop_hist: np.ndarray
-    n: np.ndarray
-    mean: np.ndarray
-    m2: np.ndarray
-    min: np.ndarray
-    max: np.ndarray
     quantiles: List[float]
     metrics: List[str]
     dc_names: List[str]
@@ -339,22 +382,14 @@ class LatencyStats:
                     sla_s) -> "LatencyStats":
         """pop_hist: [n_row, 2, 256], stats: [n_row, 2, Q + 2, 5] = {n, mean,
         M2, min, max} (tensors or arrays, on the host)."""
-        a = np.asarray(stats, dtype=np.float64)
         lo, hi = latency_bin_edges()
         qs = [float(q) for q in quantiles]
-        return cls(pop_hist=np.asarray(pop_hist).astype(np.int64),
-                   n=a[..., 0].astype(np.int64), mean=a[..., 1].copy(),
-                   m2=a[..., 2].copy(), min=a[..., 3].copy(),
-                   max=a[..., 4].copy(), quantiles=qs,
-                   metrics=[quantile_label(q) for q in qs] +
-                   ["sla_miss_frac", "jobs"],
-                   dc_names=list(dc_names), job_types=list(JOB_TYPES),
-                   bin_lo=lo, bin_hi=hi, sla_s=float(sla_s))
-
-    def to_array(self) -> np.ndarray:
-        """[n_row, 2, K, 5] float64 = {n, mean, M2, min, max}."""
-        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
-                         self.min, self.max], axis=-1)
+        return cls.from_array(
+            stats, pop_hist=np.asarray(pop_hist).astype(np.int64),
+            quantiles=qs, metrics=[quantile_label(q) for q in qs] +
+            ["sla_miss_frac", "jobs"],
+            dc_names=list(dc_names), job_types=list(JOB_TYPES),
+            bin_lo=lo, bin_hi=hi, sla_s=float(sla_s))
 
     def to_flat(self) -> np.ndarray:
         """Histogram and statistics as one f64 vector, the form that travels
@@ -376,25 +411,17 @@ class LatencyStats:
         """[n_row, 2]: quantile q of the pooled histogram."""
         return latency_quantile(self.pop_hist, q)
 
-
-def _merge_latency_pair(a: LatencyStats, b: LatencyStats) -> LatencyStats:
-    assert a.quantiles == b.quantiles and a.dc_names == b.dc_names \
-        and a.sla_s == b.sla_s
-    mean, m2 = _chan(a, b)
-    return LatencyStats(a.pop_hist + b.pop_hist, a.n + b.n, mean, m2,
-                        np.fmin(a.min, b.min), np.fmax(a.max, b.max),
-                        a.quantiles, a.metrics, a.dc_names, a.job_types,
-                        a.bin_lo, a.bin_hi, a.sla_s)
+    def merge(self, b: "LatencyStats") -> "LatencyStats":
+        assert self.quantiles == b.quantiles and \
+            self.dc_names == b.dc_names and self.sla_s == b.sla_s
+        return Moments.merge(self, b, pop_hist=self.pop_hist + b.pop_hist)
 
 
 def merge_latency_stats(parts: Sequence[LatencyStats]) -> LatencyStats:
     """Combine disjoint replica groups (shards, ranks, separate runs):
-    histograms add; n / mean / M2 merge by the Chan formula of
-    merge_series_stats in the same tree order, min and max directly."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_latency_stats needs at least one LatencyStats")
-    return _tree_merge(parts, _merge_latency_pair)
+    histograms add; the moments merge as in merge_series_stats, in the same
+    tree order."""
+    return _tree_merge(parts, LatencyStats, "merge_latency_stats")
 
 
 LATENCY_COLUMNS = ["dc", "type", "metric", "n", "mean", "std", "stderr",
@@ -411,10 +438,7 @@ def latency_frame(stats: LatencyStats, confidence: float = 0.95) -> pd.DataFrame
     D, J, K = len(stats.dc_names), len(stats.job_types), len(stats.metrics)
     n = stats.n.reshape(-1)
     mean = stats.mean.reshape(-1)
-    multi = n > 1
-    std = np.where(multi, np.sqrt(np.maximum(stats.m2.reshape(-1), 0.0)
-                                  / np.where(multi, n - 1, 1)), 0.0)
-    se = np.where(multi, std / np.sqrt(np.where(multi, n, 1)), 0.0)
+    std, se = stats.std().reshape(-1), stats.stderr().reshape(-1)
     return pd.DataFrame({
         "dc": np.repeat(np.asarray(stats.dc_names, object), J * K),
         "type": np.tile(np.repeat(np.asarray(stats.job_types, object), K), D),
@@ -490,72 +514,27 @@ def sweep_replica_metrics(t) -> np.ndarray:
 
 
 @dataclass
-class SweepStats:
-    """Per-group ensemble statistics of a sweep: ``n``, ``mean``, ``m2`` (sum
-    of squared deviations from the mean), ``min`` and ``max`` are [G,
+class SweepStats(Moments):
+    """Per-group ensemble statistics of a sweep: the moments are [G,
     len(metrics)], each over the group's replicas that have the figure (NaN
-    cells are skipped, as in LatencyStats).  Cells with n == 0 hold NaN
-    mean/min/max and m2 == 0."""
-    n: np.ndarray
-    mean: np.ndarray
-    m2: np.ndarray
-    min: np.ndarray
-    max: np.ndarray
-    metrics: List[str]
+    cells are skipped, as in LatencyStats).  ``metrics`` defaults to
+    SWEEP_METRICS."""
+    metrics: Optional[List[str]] = None
 
-    @classmethod
-    def from_values(cls, values, slices) -> "SweepStats":
-        """values: [R, K] per-replica figures; slices: one ``(a, b)`` replica
-        range per group (empty where this rank holds none of it).  Two-pass,
-        shifted by the mean: sum of (x - mean)^2."""
-        v = np.asarray(values, dtype=np.float64)
-        G, K = len(slices), v.shape[1]
-        n = np.zeros((G, K), np.int64)
-        mean, lo, hi = (np.full((G, K), np.nan) for _ in range(3))
-        m2 = np.zeros((G, K))
-        for g, (a, b) in enumerate(slices):
-            for k in range(K):
-                x = v[a:b, k]
-                x = x[~np.isnan(x)]
-                if x.size == 0:
-                    continue
-                mu = x.sum() / x.size
-                d = x - mu
-                n[g, k], mean[g, k] = x.size, mu
-                m2[g, k] = (d * d).sum()
-                lo[g, k], hi[g, k] = x.min(), x.max()
-        return cls(n, mean, m2, lo, hi, list(SWEEP_METRICS))
+    def __post_init__(self):
+        self.metrics = list(SWEEP_METRICS if self.metrics is None
+                            else self.metrics)
 
-    def to_array(self) -> np.ndarray:
-        """[G, K, 5] float64 = {n, mean, M2, min, max}."""
-        return np.stack([self.n.astype(np.float64), self.mean, self.m2,
-                         self.min, self.max], axis=-1)
-
-    @classmethod
-    def from_array(cls, a, metrics=None) -> "SweepStats":
-        """Inverse of to_array."""
-        a = np.asarray(a, dtype=np.float64)
-        return cls(a[..., 0].astype(np.int64), a[..., 1].copy(),
-                   a[..., 2].copy(), a[..., 3].copy(), a[..., 4].copy(),
-                   list(metrics if metrics is not None else SWEEP_METRICS))
-
-
-def _merge_sweep_pair(a: SweepStats, b: SweepStats) -> SweepStats:
-    assert a.metrics == b.metrics and a.n.shape == b.n.shape
-    mean, m2 = _chan(a, b)
-    return SweepStats(a.n + b.n, mean, m2, np.fmin(a.min, b.min),
-                      np.fmax(a.max, b.max), a.metrics)
+    def merge(self, b: "SweepStats") -> "SweepStats":
+        assert self.metrics == b.metrics and self.n.shape == b.n.shape
+        return Moments.merge(self, b)
 
 
 def merge_sweep_stats(parts: Sequence[SweepStats]) -> SweepStats:
     """Combine the per-group statistics of disjoint replica sets (shards,
-    ranks, separate runs of one sweep): the Chan formula of
-    merge_series_stats per group and metric, in the same tree order; min and
-    max directly."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_sweep_stats needs at least one SweepStats")
-    return _tree_merge(parts, _merge_sweep_pair)
+    ranks, separate runs of one sweep): ``Moments.merge`` per group and
+    metric, in the tree order of merge_series_stats."""
+    return _tree_merge(parts, SweepStats, "merge_sweep_stats")
 
 
 SWEEP_STAT_COLUMNS = ["n", "mean", "stderr", "ci_lo", "ci_hi"]
@@ -572,10 +551,7 @@ def sweep_frame(stats: SweepStats, sweep, confidence: float = 0.95,
     if len(df) != stats.n.shape[0]:
         raise ValueError(f"sweep has {len(df)} groups, the statistics "
                          f"{stats.n.shape[0]}")
-    multi = stats.n > 1
-    std = np.where(multi, np.sqrt(np.maximum(stats.m2, 0.0)
-                                  / np.where(multi, stats.n - 1, 1)), 0.0)
-    se = np.where(multi, std / np.sqrt(np.where(multi, stats.n, 1)), 0.0)
+    se = stats.stderr()
     for k, m in enumerate(stats.metrics):
         df[f"{m}_n"] = stats.n[:, k]
         df[f"{m}_mean"] = stats.mean[:, k]

@@ -462,6 +462,20 @@ class BatchedEngine:
             raise RuntimeError("engine was built without sweep=")
         return self.sweep.slice_of(int(group), self.shard)
 
+    def _over_ranks(self, local, rebuild, merge):
+        """One statistic over the whole ensemble.  ``local(gather)`` gives
+        this rank's result when ``gather`` is false (no torch.distributed, or
+        one rank: returned as is) and otherwise its flat f64 vector, of the
+        same length on every rank; ``rebuild`` turns each rank's vector (a
+        host tensor) back into a result and ``merge`` combines them, so every
+        rank holds the global one."""
+        from ..parallel.dist import allgather_series_stats, is_distributed
+        gather = self.world > 1 and is_distributed()
+        mine = local(gather)
+        if not gather:
+            return mine
+        return merge([rebuild(p.cpu()) for p in allgather_series_stats(mine)])
+
     def sweep_stats(self):
         """Per-group statistics of the headline outcomes as a SweepStats
         (analysis/montecarlo.py): n / mean / M2 / min / max over each group's
@@ -472,7 +486,6 @@ class BatchedEngine:
         from ..analysis.montecarlo import (SWEEP_METRICS, SweepStats,
                                            merge_sweep_stats,
                                            sweep_replica_metrics)
-        from ..parallel.dist import allgather_series_stats, is_distributed
         if self.sweep is None:
             raise RuntimeError("engine was built without sweep=")
         vals = sweep_replica_metrics({k: self.t[k].cpu().numpy() for k in (
@@ -481,14 +494,12 @@ class BatchedEngine:
         G = self.sweep.n_groups
         mine = SweepStats.from_values(
             vals, [self.sweep.slice_of(g, self.shard) for g in range(G)])
-        if not (self.world > 1 and is_distributed()):
-            return mine
-        parts = allgather_series_stats(
-            torch.from_numpy(mine.to_array().reshape(-1)))
-        return merge_sweep_stats(
-            [SweepStats.from_array(
-                p.cpu().numpy().reshape(G, len(SWEEP_METRICS), 5))
-             for p in parts])
+        return self._over_ranks(
+            lambda gather: torch.from_numpy(mine.to_array().reshape(-1))
+            if gather else mine,
+            lambda p: SweepStats.from_array(
+                p.numpy().reshape(G, len(SWEEP_METRICS), 5)),
+            merge_sweep_stats)
 
     def population_series(self, group=None):
         """Per-tick statistics over the replica ensemble as a SeriesStats
@@ -500,12 +511,17 @@ class BatchedEngine:
         series.  ``group=g`` (sweep engines): over that group's replicas on
         this rank only."""
         from ..analysis.montecarlo import SeriesStats, merge_series_stats
-        from ..parallel.dist import allgather_series_stats, is_distributed
         ps = self.pop_samples()
         every = self.pop_series_every
         cap = int(ps["samples"].shape[0])
         n_row, K = self.sc.n_dc + 1, len(SERIES_METRICS)
         names = list(self.sc.dc_names) + [SERIES_FLEET]
+
+        def wrap(flat_stats, time):
+            return SeriesStats.from_tensor(
+                flat_stats.view(len(time), n_row, K, 5), time,
+                metrics=list(SERIES_METRICS), dc_names=names)
+
         if group is not None:
             a, b = self._group_slice(group)
             if b <= a:
@@ -516,26 +532,21 @@ class BatchedEngine:
             smp = ps["samples"][:T, :, :, a:b].contiguous()
             raw = self._mod.reduce_series(
                 smp.view(T, n_row * K, b - a), ticks, every)
-            return SeriesStats.from_tensor(
-                raw.cpu().view(T, n_row, K, 5), ps["time"][:T].cpu(),
-                metrics=list(SERIES_METRICS), dc_names=names).trimmed()
-        dist_on = self.world > 1 and is_distributed()
-        # ranks must agree on the shape they gather: the full buffer then
-        T = cap if dist_on else min(cap, int(ps["ticks"].max().item()) // every)
-        raw = self._mod.reduce_series(
-            ps["samples"][:T].view(T, n_row * K, self.R), ps["ticks"], every)
-
-        def wrap(flat_stats, time):
-            return SeriesStats.from_tensor(
-                flat_stats.view(T, n_row, K, 5), time,
-                metrics=list(SERIES_METRICS), dc_names=names)
-
-        if not dist_on:
             return wrap(raw.cpu(), ps["time"][:T].cpu()).trimmed()
-        flat = torch.cat([raw.reshape(-1), ps["time"][:T]])
-        parts = [p.cpu() for p in allgather_series_stats(flat)]
-        return merge_series_stats(
-            [wrap(p[:-T], p[-T:]) for p in parts]).trimmed()
+
+        def local(gather):
+            # ranks must agree on the shape they gather: the full buffer then
+            T = cap if gather else \
+                min(cap, int(ps["ticks"].max().item()) // every)
+            raw = self._mod.reduce_series(
+                ps["samples"][:T].view(T, n_row * K, self.R), ps["ticks"],
+                every)
+            if gather:
+                return torch.cat([raw.reshape(-1), ps["time"][:T]])
+            return wrap(raw.cpu(), ps["time"][:T].cpu())
+
+        return self._over_ranks(local, lambda p: wrap(p[:-cap], p[-cap:]),
+                                merge_series_stats).trimmed()
 
     # ---------------- latency histograms ----------------
     def latency_hist(self):
@@ -557,7 +568,6 @@ class BatchedEngine:
         merged, so every rank holds the global one.  ``group=g`` (sweep
         engines): over that group's replicas on this rank only."""
         from ..analysis.montecarlo import LatencyStats, merge_latency_stats
-        from ..parallel.dist import allgather_series_stats, is_distributed
         lh = self.latency_hist()
         qs = [float(q) for q in quantiles]
         hist, over = lh["hist"], lh["over"]
@@ -573,13 +583,15 @@ class BatchedEngine:
         mine = LatencyStats.from_tensor(
             pop.cpu().view(n_row, 2, LH_BINS), stats.cpu().view(n_row, 2, K, 5),
             quantiles=qs, dc_names=names, sla_s=lh["sla_s"])
-        if group is not None or not (self.world > 1 and is_distributed()):
+        if group is not None:
             return mine
         # the histogram travels as f64 with the statistics: exact below 2^53
-        parts = allgather_series_stats(torch.from_numpy(mine.to_flat()))
-        return merge_latency_stats(
-            [LatencyStats.from_flat(p.cpu().numpy(), qs, names, lh["sla_s"])
-             for p in parts])
+        return self._over_ranks(
+            lambda gather: torch.from_numpy(mine.to_flat()) if gather
+            else mine,
+            lambda p: LatencyStats.from_flat(p.numpy(), qs, names,
+                                             lh["sla_s"]),
+            merge_latency_stats)
 
     # ---------------- state checkpointing (capability extension) ----------
     def save_state(self, path: str):

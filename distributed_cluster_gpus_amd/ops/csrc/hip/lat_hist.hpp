@@ -27,21 +27,19 @@
 // load the 256 bins as one coalesced 1 KiB row, 4 bins (16 B) per lane, the
 // fleet row adds the n_dc rows the same way; a shuffle scan gives every lane
 // its cumulative counts, and for each rank a ballot finds the first lane that
-// reaches it.  lat_stats_kernel is reduce_series_kernel's shifted two-pass,
-// fixed-order scheme over the replica axis with "is not NaN" as the mask, so
-// it is bitwise reproducible for a given replica count.
+// reaches it.  lat_stats_kernel is the shared ensemble reduction of
+// moments.hpp over the replica axis with "is not NaN" as the mask, so it is
+// bitwise reproducible for a given replica count.
 #pragma once
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <stdexcept>
-#include <string>
 #include <tuple>
 
 #include "lat_bins.hpp"
-#include "pop_series.hpp"
+#include "moments.hpp"
 #include "sim_models.hpp"
 
 namespace dcg {
@@ -70,8 +68,8 @@ constexpr int LH_PER_LANE = LH_BINS / 64;  // 4 bins = one 16-byte load
 constexpr int LH_THREADS = 256;
 constexpr int LH_POP_CHUNK = 64;           // replicas per lat_pop_kernel block
 static_assert(LH_PER_LANE == 4, "one int4 load per lane covers the row");
-static_assert(LH_THREADS == LH_BINS && LH_THREADS == PS_THREADS,
-              "lat_pop_kernel: a thread per bin; lat_stats_kernel: ps_block_*");
+static_assert(LH_THREADS == LH_BINS && LH_THREADS == MOM_THREADS,
+              "lat_pop_kernel: a thread per bin; lat_stats_kernel: block_moments");
 
 struct LatQuantiles {
   double q[LH_MAX_Q];
@@ -166,59 +164,16 @@ lat_pop_kernel(const int* __restrict__ hist, int n_rep, int n_dc,
 }
 
 // {n, mean, M2, min, max} of one per_rep row over the replicas whose value is
-// not NaN: reduce_series_kernel's scheme with that mask
+// not NaN
 __global__ void __launch_bounds__(LH_THREADS)
 lat_stats_kernel(const double* __restrict__ per_rep, int n_rep,
                  double* __restrict__ stats) {
-  __shared__ double l_buf[PS_WAVES];
+  __shared__ double l_buf[MOM_WAVES];
   const int64_t cell = blockIdx.x;  // c * K + k
   const double* row = per_rep + cell * (int64_t)n_rep;
-
-  double cnt = 0.0, first = (double)n_rep;
-  for (int r = threadIdx.x; r < n_rep; r += LH_THREADS) {
-    if (row[r] == row[r]) {
-      cnt += 1.0;
-      first = fmin(first, (double)r);
-    }
-  }
-  const double n = ps_block_sum(cnt, l_buf);  // exact: counts < 2^53
-  const int r0 = (int)ps_block_min(first, l_buf);
-  // an infinite shift would turn inf - inf into NaN; such a row's mean is
-  // infinite (or NaN) either way
-  double x0 = r0 < n_rep ? row[r0] : 0.0;
-  if (isinf(x0)) x0 = 0.0;
-
-  double sum = 0.0;
-  for (int r = threadIdx.x; r < n_rep; r += LH_THREADS) {
-    double x = row[r];
-    if (x == x) sum += x - x0;
-  }
-  sum = ps_block_sum(sum, l_buf);
-  const double mean = x0 + sum / n;  // n == 0: overwritten below
-
-  double m2 = 0.0, lo = INFINITY, hi = -INFINITY;
-  for (int r = threadIdx.x; r < n_rep; r += LH_THREADS) {
-    double x = row[r];
-    if (x == x) {
-      double dx = x - mean;
-      m2 += dx * dx;
-      lo = fmin(lo, x);
-      hi = fmax(hi, x);
-    }
-  }
-  m2 = ps_block_sum(m2, l_buf);
-  lo = ps_block_min(lo, l_buf);
-  hi = -ps_block_min(-hi, l_buf);
-  if (threadIdx.x == 0) {
-    double* out = stats + cell * PS_STATS;
-    const bool any = n > 0.0;
-    const double qnan = __builtin_nan("");
-    out[0] = n;
-    out[1] = any ? mean : qnan;
-    out[2] = any ? m2 : 0.0;
-    out[3] = any ? lo : qnan;
-    out[4] = any ? hi : qnan;
-  }
+  block_moments<true>(
+      row, n_rep, l_buf, [=](int r) { return row[r] == row[r]; },
+      stats, cell);
 }
 
 // (hist[R, D, 2, B] i32, over[R, D, 2] i32, qs[Q] f64 on any device,
@@ -258,7 +213,7 @@ inline std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> latency_reduce(
   auto pop = torch::zeros({C, (int64_t)LH_BINS},
                           hist.options().dtype(torch::kInt64));
   auto per_rep = torch::empty({C, K, R}, hist.options().dtype(torch::kFloat64));
-  auto stats = torch::empty({C, K, (int64_t)PS_STATS}, per_rep.options());
+  auto stats = torch::empty({C, K, (int64_t)MOM_STATS}, per_rep.options());
   hipStream_t stream = at::hip::getCurrentHIPStream();
   const int64_t waves = R * C, per_block = LH_THREADS / 64;
   hipLaunchKernelGGL(lat_cell_kernel,
@@ -274,10 +229,7 @@ inline std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> latency_reduce(
   hipLaunchKernelGGL(lat_stats_kernel, dim3((unsigned)(C * K)),
                      dim3(LH_THREADS), 0, stream, per_rep.data_ptr<double>(),
                      (int)R, stats.data_ptr<double>());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("latency_reduce: ") +
-                             hipGetErrorString(e));
+  check_launch("latency_reduce");
   return {pop, per_rep, stats};
 }
 

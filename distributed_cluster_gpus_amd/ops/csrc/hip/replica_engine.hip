@@ -44,6 +44,7 @@
 #include "engine_limits.hpp"
 #include "lat_hist.hpp"
 #include "launch_plan.hpp"
+#include "moments.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
 #include "sim_models.hpp"
@@ -2107,13 +2108,6 @@ rl_forward_mfma_kernel(const float* pw, const float* obs, int B, int obs_dim,
       }
     }
   }
-}
-
-// throw if the kernel launch just issued failed
-static void check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
 std::vector<torch::Tensor> rl_forward_mfma(torch::Tensor pw,

@@ -1,6 +1,7 @@
 """Analysis-layer tests: run loading, aggregation, all figure artifacts."""
 import os
 
+import numpy as np
 import pandas as pd
 import pytest
 
@@ -125,3 +126,106 @@ def test_violin_and_boxen_render(tmp_path):
         if have_mpl():
             assert os.path.exists(os.path.join(str(tmp_path),
                                                f"lat_{kind}.png"))
+
+
+# ---------------- the shared ensemble moments ----------------
+MOMENT_FIELDS = ("n", "mean", "m2", "min", "max")
+
+
+def _wrap_three(a):
+    """The same [4, 3, 5] cell array as a SeriesStats (4 ticks x 3 DCs x 1
+    metric), a LatencyStats (2 rows x 2 job types x 3 figures, empty
+    histograms) and a SweepStats (4 groups x 3 metrics)."""
+    from distributed_cluster_gpus_amd.analysis.montecarlo import (
+        LH_BINS, LatencyStats, SeriesStats, SweepStats)
+    return (
+        SeriesStats.from_tensor(a.reshape(4, 3, 1, 5), np.arange(4.0),
+                                metrics=["m"], dc_names=["a", "b", "ALL"]),
+        LatencyStats.from_tensor(np.zeros((2, 2, LH_BINS), np.int64),
+                                 a.reshape(2, 2, 3, 5), quantiles=[0.5],
+                                 dc_names=["a", "ALL"], sla_s=1.0),
+        SweepStats.from_array(a, metrics=["x", "y", "z"]))
+
+
+def test_one_merge_behind_the_three_statistics():
+    """merge_series_stats, merge_latency_stats and merge_sweep_stats over the
+    same cells give the same bytes, those of Moments.merge folded in the same
+    tree order; some cells are empty on one side, on both, or hold one
+    replica."""
+    from distributed_cluster_gpus_amd.analysis.montecarlo import (
+        Moments, merge_latency_stats, merge_series_stats, merge_sweep_stats)
+    rng = np.random.default_rng(11)
+    x = rng.normal(size=(10, 4, 3)) * 3.0 + 1e6
+    x[:, 0, 0] = np.nan           # no replica has the figure: n = 0 everywhere
+    x[1:, 0, 1] = np.nan          # one replica has it: n = 1 in one part
+    x[:5, 0, 2] = np.nan          # the first parts hold none of it
+    x[::3, 2, 1] = np.nan
+
+    def cells(rows):
+        m = Moments.from_values(x[rows].reshape(len(rows), 12),
+                                [(0, len(rows))])
+        return m.to_array().reshape(4, 3, 5)
+
+    for k in (1, 2, 3, 5):
+        arrays = [cells(rows) for rows in np.array_split(np.arange(10), k)]
+        n = np.stack([a[..., 0] for a in arrays])
+        assert (n[:, 0, 0] == 0).all() and sorted(n[:, 0, 1])[-1] == 1
+        if k > 1:
+            assert n[0, 0, 2] == 0 and n[-1, 0, 2] > 0
+        ref = [Moments.from_array(a) for a in arrays]
+        while len(ref) > 1:
+            nxt = [Moments.merge(ref[i], ref[i + 1])
+                   for i in range(0, len(ref) - 1, 2)]
+            ref = nxt + ref[len(ref) - len(ref) % 2:]
+        wrapped = [_wrap_three(a) for a in arrays]
+        merged = (merge_series_stats([w[0] for w in wrapped]),
+                  merge_latency_stats([w[1] for w in wrapped]),
+                  merge_sweep_stats([w[2] for w in wrapped]))
+        for f in MOMENT_FIELDS:
+            want = getattr(ref[0], f)
+            assert want.dtype == (np.int64 if f == "n" else np.float64)
+            for got in merged:
+                assert getattr(got, f).dtype == want.dtype
+                assert getattr(got, f).tobytes() == want.tobytes(), (k, f)
+        # the whole ensemble, reduced in one piece
+        whole = cells(np.arange(10))
+        assert np.array_equal(merged[2].n, whole[..., 0])
+        np.testing.assert_allclose(merged[2].mean, whole[..., 1], rtol=1e-12)
+
+
+def test_one_spread_behind_the_three_frames():
+    """std / stderr are 0 where n < 2 and never NaN, also where rounding left
+    a tiny negative m2; the three frames print the same error bars."""
+    from distributed_cluster_gpus_amd.analysis.montecarlo import (
+        LH_BINS, LatencyStats, Moments, SeriesStats, SweepStats,
+        latency_frame, series_frame, sweep_frame)
+    from distributed_cluster_gpus_amd.engine.sweep import Sweep
+    n = np.array([0, 1, 2, 7, 0, 1, 2, 7], np.int64)
+    m2 = np.array([0.0, 0.0, -1e-18, -1e-18, 0.0, -1e-18, 3.0, 12.5])
+    mean = np.where(n > 0, 5.0 + np.arange(8), np.nan)
+    a = np.stack([n.astype(np.float64), mean, m2, mean - 1, mean + 1],
+                 axis=-1)
+    m = Moments.from_array(a)
+    std, se = m.std(), m.stderr()
+    assert not np.isnan(std).any() and not np.isnan(se).any()
+    assert (std[n < 2] == 0).all() and (se[n < 2] == 0).all()
+    assert (std[:6] == 0).all() and (se[:6] == 0).all()   # clamped m2
+    assert std[6] == np.sqrt(3.0 / 1) and se[6] == std[6] / np.sqrt(2)
+    assert std[7] == np.sqrt(12.5 / 6) and se[7] == std[7] / np.sqrt(7)
+
+    sf = series_frame(SeriesStats.from_tensor(
+        a.reshape(8, 1, 1, 5), np.arange(8.0), metrics=["m"],
+        dc_names=["ALL"]))
+    lf = latency_frame(LatencyStats.from_tensor(
+        np.zeros((2, 2, LH_BINS), np.int64), a.reshape(2, 2, 2, 5),
+        quantiles=[], dc_names=["a", "ALL"], sla_s=1.0))
+    wf = sweep_frame(SweepStats.from_array(a.reshape(8, 1, 5), metrics=["m"]),
+                     Sweep.grid(inf_rate=list(range(1, 9))))
+    z = 1.96
+    want = {"std": std, "stderr": se, "ci_lo": mean - z * se,
+            "ci_hi": mean + z * se}
+    for col, w in want.items():
+        assert sf[col].to_numpy().tobytes() == w.tobytes(), col
+        assert lf[col].to_numpy().tobytes() == w.tobytes(), col
+        if col != "std":          # sweep_frame has no std column
+            assert wf[f"m_{col}"].to_numpy().tobytes() == w.tobytes(), col
