@@ -47,6 +47,7 @@
 #include "moments.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
+#include "sac_target.hpp"
 #include "sim_models.hpp"
 
 namespace dcg {
@@ -2799,5 +2800,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",
         py::arg("pw"), py::arg("obs"), py::arg("hid"), py::arg("n_dc"),
         py::arg("n_g"));
+  m.def("sac_td_target", &dcg::sac_td_target,
+        "fused SAC TD target on the matrix cores (weights[26] = (weight, "
+        "bias) of encoder x3, head_dc x2, head_g x2, target q1 x3, q2 x3; "
+        "s_next[B,D]; mask_dc, mask_g bool or None; u_dc, u_g uniforms; "
+        "r_eff[B]; done[B]; log_alpha 0-dim on the device; gamma) -> "
+        "(target[B,N], a_dc[B] i64, a_g[B] i64, logp[B])",
+        py::arg("weights"), py::arg("s_next"), py::arg("mask_dc"),
+        py::arg("mask_g"), py::arg("u_dc"), py::arg("u_g"), py::arg("r_eff"),
+        py::arg("done"), py::arg("log_alpha"), py::arg("gamma"));
+  m.def("qr_huber_twin", &dcg::qr_huber_twin,
+        "twin quantile-Huber loss and its gradient in one pass (q1, q2, "
+        "target [B,N]; taus [N]) -> (loss 0-dim, dloss/dq1, dloss/dq2)",
+        py::arg("q1"), py::arg("q2"), py::arg("target"), py::arg("taus"));
   dcg::bind_debug_entries(m);
 }

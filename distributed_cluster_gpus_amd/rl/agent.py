@@ -35,6 +35,7 @@ class CHSACAgentConfig:
     actor_lr: float = 3e-4
     critic_lr: float = 3e-4
     graph_capturable: bool = False  # Adam capturable state (hipGraph path)
+    fused_critic: bool = False  # HIP kernels for the critic phase (rl/fused.py)
 
 
 class CHSACAgent:
@@ -49,7 +50,8 @@ class CHSACAgent:
                                     n_quantiles=cfg.n_quantiles, alpha=cfg.alpha,
                                     actor_lr=cfg.actor_lr, critic_lr=cfg.critic_lr,
                                     device=self.device,
-                                    capturable=cfg.graph_capturable)
+                                    capturable=cfg.graph_capturable,
+                                    fused_critic=cfg.fused_critic)
         self.cmdp = PIDLagrangian(
             {k: Constraint(name=k, target=v) for k, v in cfg.constraints.items()},
             device=cfg.device)

@@ -1,0 +1,118 @@
+"""Fused matrix-core kernels for the SAC critic phase (opt-in).
+
+Two blocks of ``MaskedHybridSAC._critic_phase`` need no autograd graph through
+the networks, and each is one HIP kernel (ops/csrc/hip/sac_target.hpp):
+
+* ``sac_td_target`` — encoder(s_next), both actor heads, masked Gumbel-max
+  draws, the twin target critic, min, entropy term and the TD line, with the
+  activations in LDS from ``s_next`` to the target quantiles;
+* ``qr_huber_twin`` — the twin quantile-Huber loss and its closed-form
+  gradient in one pass, wrapped here in an autograd Function.
+
+``MaskedHybridSAC(fused_critic=True)`` takes this path when ``unusable``
+returns None, and warns once and keeps the torch path otherwise.
+"""
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+
+from .networks import HybridActor, StateEncoder, TwinQuantileCritic
+
+# the kernels' accepted shapes (TORCH_CHECKed again before any launch)
+MAX_WIDTH, MAX_ACTIONS, MAX_QUANTILES = 256, 16, 64
+
+
+def target_linears(algo) -> List[nn.Linear]:
+    """The 13 Linear layers of the target chain, in the kernel's order."""
+    enc, act, tc = algo.encoder.net, algo.actor, algo.target_critic
+    return [enc[0], enc[2], enc[4],
+            act.head_dc[0], act.head_dc[2], act.head_g[0], act.head_g[2],
+            tc.q1[0], tc.q1[2], tc.q1[4], tc.q2[0], tc.q2[2], tc.q2[4]]
+
+
+def target_weights(algo) -> List[torch.Tensor]:
+    """(weight, bias) of ``target_linears`` — the parameters' own storage, so
+    in-place Adam and polyak updates are seen without any copy."""
+    out = []
+    for lin in target_linears(algo):
+        out += [lin.weight.detach(), lin.bias.detach()]
+    return out
+
+
+def unusable(algo) -> Optional[str]:
+    """Why the fused critic phase cannot serve ``algo`` (None: it can)."""
+    if algo.device.type != "cuda":
+        return f"the agent is on {algo.device}, not on a GPU"
+    if not (type(algo.encoder) is StateEncoder
+            and type(algo.actor) is HybridActor
+            and type(algo.critic) is TwinQuantileCritic):
+        return "the networks are not the standard encoder/actor/critic stacks"
+    try:
+        shapes = [tuple(lin.weight.shape) for lin in target_linears(algo)]
+        typed = all(type(lin) is nn.Linear and lin.bias is not None
+                    and lin.weight.dtype == torch.float32
+                    for lin in target_linears(algo))
+    except (AttributeError, IndexError, TypeError):
+        return "the networks are not the standard encoder/actor/critic stacks"
+    H, D = shapes[0]
+    n_dc, n_g, N = shapes[4][0], shapes[6][0], shapes[9][0]
+    C = H + n_dc + n_g
+    want = [(H, D), (H, H), (H, H), (H, H), (n_dc, H), (H, H), (n_g, H),
+            (H, C), (H, H), (N, H), (H, C), (H, H), (N, H)]
+    if not typed or shapes != want:
+        return "the layers are not all hid = latent wide f32 Linears"
+    if H % 16 or H > MAX_WIDTH or not 1 <= D <= MAX_WIDTH:
+        return f"hid = {H} / obs_dim = {D} outside the kernel's range"
+    if max(n_dc, n_g) > MAX_ACTIONS or N > MAX_QUANTILES:
+        return f"n_dc = {n_dc}, n_g = {n_g}, N = {N} outside the kernel's range"
+    try:
+        from ..ops import load_sim_hip
+        mod = load_sim_hip()
+    except ImportError as e:
+        return f"the HIP extension does not load ({e})"
+    if not hasattr(mod, "sac_td_target"):
+        return "the HIP extension predates the fused critic kernels"
+    return None
+
+
+def _mod():
+    from ..ops import load_sim_hip
+    return load_sim_hip()
+
+
+@torch.no_grad()
+def td_target(algo, s_next, mask_dc, mask_g, r_eff, done, gamma):
+    """TD target quantiles [B, N] of one batch.  Draws u_dc then u_g exactly
+    as the two ``rand_like`` calls of the torch path do, so both consume the
+    device generator alike."""
+    B = s_next.shape[0]
+    u_dc = torch.rand(B, algo.actor.n_dc, device=s_next.device)
+    u_g = torch.rand(B, algo.actor.n_g, device=s_next.device)
+
+    def m(mask):
+        return None if mask is None else mask.bool().contiguous()
+    target, _, _, _ = _mod().sac_td_target(
+        target_weights(algo), s_next.float().contiguous(), m(mask_dc),
+        m(mask_g), u_dc, u_g, r_eff.reshape(-1).contiguous(),
+        done.reshape(-1).contiguous(), algo.log_alpha.detach(), float(gamma))
+    return target
+
+
+class _QRHuberTwin(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q1, q2, target, taus):
+        loss, dq1, dq2 = _mod().qr_huber_twin(q1, q2, target, taus)
+        ctx.save_for_backward(dq1, dq2)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dq1, dq2 = ctx.saved_tensors
+        return grad_output * dq1, grad_output * dq2, None, None
+
+
+def qr_huber_twin(q1, q2, target, taus) -> torch.Tensor:
+    """quantile_huber_loss(q1, target, taus) + quantile_huber_loss(q2, ...),
+    differentiable in q1 and q2."""
+    return _QRHuberTwin.apply(q1, q2, target, taus)

@@ -13,12 +13,14 @@ all-reduce per optimizer step is the right shape for the xGMI mesh
 (latency-bound, not ring-bandwidth-bound).
 """
 import math
+import warnings
 from typing import Callable, Dict, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import fused
 from .masking import sample_categorical
 from .networks import HybridActor, StateEncoder, TwinQuantileCritic
 
@@ -44,7 +46,8 @@ class MaskedHybridSAC(nn.Module):
     def __init__(self, encoder: StateEncoder, actor: HybridActor,
                  critic: TwinQuantileCritic, n_quantiles: int = 32,
                  alpha: float = 0.2, actor_lr: float = 3e-4, critic_lr: float = 3e-4,
-                 device: Optional[torch.device] = None, capturable: bool = False):
+                 device: Optional[torch.device] = None, capturable: bool = False,
+                 fused_critic: bool = False):
         super().__init__()
         self.encoder, self.actor, self.critic = encoder, actor, critic
         self.target_critic = TwinQuantileCritic(encoder.out_dim, actor.n_dc,
@@ -68,6 +71,22 @@ class MaskedHybridSAC(nn.Module):
         # optional distributed-gradient hook, called after each backward with
         # the parameter list whose grads must be averaged across ranks.
         self.allreduce_hook: Optional[Callable] = None
+        # opt-in fused critic phase (rl/fused.py): TD target and twin QR-Huber
+        # loss as HIP kernels.  Decided at the first update; if the kernels
+        # cannot serve this agent, warn once and keep the torch path.
+        self.fused_critic = bool(fused_critic)
+        self._fused_ready: Optional[bool] = None
+
+    def _use_fused(self) -> bool:
+        if not self.fused_critic:
+            return False
+        if self._fused_ready is None:
+            why = fused.unusable(self)
+            if why is not None:
+                warnings.warn(f"fused_critic unavailable: {why}; "
+                              "falling back to the torch critic phase")
+            self._fused_ready = why is None
+        return self._fused_ready
 
     @property
     def alpha(self) -> torch.Tensor:
@@ -116,14 +135,20 @@ class MaskedHybridSAC(nn.Module):
                       mask_dc_n, mask_g_n):
         """QR-Huber TD loss against entropy-regularized target quantiles."""
         h = self.encoder(s)
-        h_next = self.encoder(s_next).detach()
-        with torch.no_grad():
-            q_next, _ = self._target_quantiles(h_next, mask_dc_n, mask_g_n)
-            target = (r_eff + (1 - done) * gamma * q_next).detach()
-        q1, q2 = self.critic(h, a_dc, a_g)
         taus = self.taus.to(self.device)
-        loss = quantile_huber_loss(q1, target, taus) + \
-            quantile_huber_loss(q2, target, taus)
+        if self._use_fused():
+            target = fused.td_target(self, s_next, mask_dc_n, mask_g_n,
+                                     r_eff, done, gamma)
+            q1, q2 = self.critic(h, a_dc, a_g)
+            loss = fused.qr_huber_twin(q1, q2, target, taus)
+        else:
+            h_next = self.encoder(s_next).detach()
+            with torch.no_grad():
+                q_next, _ = self._target_quantiles(h_next, mask_dc_n, mask_g_n)
+                target = (r_eff + (1 - done) * gamma * q_next).detach()
+            q1, q2 = self.critic(h, a_dc, a_g)
+            loss = quantile_huber_loss(q1, target, taus) + \
+                quantile_huber_loss(q2, target, taus)
         self._optimize(self.critic_opt, loss, list(self.critic.parameters()))
         return loss
 

@@ -33,6 +33,8 @@ def main(argv=None):
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--train-interval", type=int, default=256)
     p.add_argument("--seed", type=int, default=123)
+    p.add_argument("--fused-critic", action="store_true", default=False,
+                   help="fused HIP kernels for the SAC critic phase")
     p.add_argument("--checkpoint", type=str, default="chsac_dp.pt")
     p.add_argument("--replay-npz", type=str, default=None,
                    help="also dump the replay ring as an offline .npz dataset")
@@ -60,7 +62,8 @@ def main(argv=None):
                         out_dir=None, seed=args.seed, device=device,
                         rank=rank, world=world, enable_logs=False,
                         rl_warmup=args.warmup, rl_batch=args.batch,
-                        rl_train_interval=args.train_interval)
+                        rl_train_interval=args.train_interval,
+                        rl_fused_critic=args.fused_critic)
     # replicate the agent across ranks, then train data-parallel
     for mod in (eng.rl.encoder, eng.rl.actor, eng.rl.critic,
                 eng.rl.algo.target_critic):
