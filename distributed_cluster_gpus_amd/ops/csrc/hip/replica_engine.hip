@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "arrival_ring.hpp"
+#include "critic_mlp.hpp"
 #include "engine_bind.hpp"
 #include "engine_desc.hpp"
 #include "engine_limits.hpp"
@@ -2813,5 +2814,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "twin quantile-Huber loss and its gradient in one pass (q1, q2, "
         "target [B,N]; taus [N]) -> (loss 0-dim, dloss/dq1, dloss/dq2)",
         py::arg("q1"), py::arg("q2"), py::arg("target"), py::arg("taus"));
+  m.def("twin_critic_fwd", &dcg::twin_critic_fwd,
+        "twin quantile critic forward that keeps its activations (weights[12] "
+        "= (weight, bias) of q1 x3, q2 x3; h[B,H]; a_dc, a_g [B] i64; n_dc; "
+        "n_g) -> (q1[B,N], q2[B,N], act[2,2,B,H])",
+        py::arg("weights"), py::arg("h"), py::arg("a_dc"), py::arg("a_g"),
+        py::arg("n_dc"), py::arg("n_g"));
+  m.def("twin_critic_bwd", &dcg::twin_critic_bwd,
+        "twin quantile critic backward (weights[12], h, a_dc, a_g, n_dc, n_g, "
+        "act, dq1, dq2, want_dh, want_dw) -> (dh[B,H] or None, grads[12] in "
+        "the order of weights, or [])",
+        py::arg("weights"), py::arg("h"), py::arg("a_dc"), py::arg("a_g"),
+        py::arg("n_dc"), py::arg("n_g"), py::arg("act"), py::arg("dq1"),
+        py::arg("dq2"), py::arg("want_dh"), py::arg("want_dw"));
   dcg::bind_debug_entries(m);
 }

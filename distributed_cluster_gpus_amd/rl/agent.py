@@ -36,6 +36,7 @@ class CHSACAgentConfig:
     critic_lr: float = 3e-4
     graph_capturable: bool = False  # Adam capturable state (hipGraph path)
     fused_critic: bool = False  # HIP kernels for the critic phase (rl/fused.py)
+    fused_critic_mlp: bool = False  # HIP twin critic, forward and backward
 
 
 class CHSACAgent:
@@ -51,7 +52,8 @@ class CHSACAgent:
                                     actor_lr=cfg.actor_lr, critic_lr=cfg.critic_lr,
                                     device=self.device,
                                     capturable=cfg.graph_capturable,
-                                    fused_critic=cfg.fused_critic)
+                                    fused_critic=cfg.fused_critic,
+                                    fused_critic_mlp=cfg.fused_critic_mlp)
         self.cmdp = PIDLagrangian(
             {k: Constraint(name=k, target=v) for k, v in cfg.constraints.items()},
             device=cfg.device)

@@ -11,6 +11,12 @@ the networks, and each is one HIP kernel (ops/csrc/hip/sac_target.hpp):
 
 ``MaskedHybridSAC(fused_critic=True)`` takes this path when ``unusable``
 returns None, and warns once and keeps the torch path otherwise.
+
+``MaskedHybridSAC(fused_critic_mlp=True)`` (independent of the above) also
+runs the twin critic itself in HIP (ops/csrc/hip/critic_mlp.hpp):
+``twin_critic`` is an autograd Function over a forward kernel that keeps its
+activations, a backward kernel for dz and dh, and a weight-gradient kernel
+that is launched only when the critic's parameters ask for gradients.
 """
 from typing import List, Optional
 
@@ -40,8 +46,16 @@ def target_weights(algo) -> List[torch.Tensor]:
     return out
 
 
-def unusable(algo) -> Optional[str]:
-    """Why the fused critic phase cannot serve ``algo`` (None: it can)."""
+def critic_linears(critic) -> List[nn.Linear]:
+    """The 6 Linear layers of a twin critic, in the kernels' order."""
+    return [critic.q1[0], critic.q1[2], critic.q1[4],
+            critic.q2[0], critic.q2[2], critic.q2[4]]
+
+
+def unusable(algo, entry: str = "sac_td_target") -> Optional[str]:
+    """Why the fused critic phase cannot serve ``algo`` (None: it can).
+    ``entry`` is the extension function the caller needs: the trainable
+    critic MLP asks for ``twin_critic_fwd``."""
     if algo.device.type != "cuda":
         return f"the agent is on {algo.device}, not on a GPU"
     if not (type(algo.encoder) is StateEncoder
@@ -71,8 +85,8 @@ def unusable(algo) -> Optional[str]:
         mod = load_sim_hip()
     except ImportError as e:
         return f"the HIP extension does not load ({e})"
-    if not hasattr(mod, "sac_td_target"):
-        return "the HIP extension predates the fused critic kernels"
+    if not hasattr(mod, entry):
+        return f"the HIP extension predates the fused critic kernels ({entry})"
     return None
 
 
@@ -116,3 +130,43 @@ def qr_huber_twin(q1, q2, target, taus) -> torch.Tensor:
     """quantile_huber_loss(q1, target, taus) + quantile_huber_loss(q2, ...),
     differentiable in q1 and q2."""
     return _QRHuberTwin.apply(q1, q2, target, taus)
+
+
+class _TwinCritic(torch.autograd.Function):
+    """(h, a_dc, a_g, n_dc, n_g, *weights[12]) -> (q1, q2).  The backward
+    computes only what autograd asks for: dh if h needs a gradient, the twelve
+    weight and bias gradients if any weight does."""
+
+    @staticmethod
+    def forward(ctx, h, a_dc, a_g, n_dc, n_g, *weights):
+        q1, q2, act = _mod().twin_critic_fwd(list(weights), h, a_dc, a_g,
+                                             n_dc, n_g)
+        ctx.save_for_backward(h, a_dc, a_g, act, *weights)
+        ctx.n = (n_dc, n_g)
+        return q1, q2
+
+    @staticmethod
+    def backward(ctx, dq1, dq2):
+        h, a_dc, a_g, act, *weights = ctx.saved_tensors
+        want_dh = ctx.needs_input_grad[0]
+        want_dw = any(ctx.needs_input_grad[5:])
+        dh, grads = _mod().twin_critic_bwd(
+            weights, h, a_dc, a_g, *ctx.n, act, dq1.contiguous(),
+            dq2.contiguous(), want_dh, want_dw)
+        return (dh, None, None, None, None, *(grads or [None] * 12))
+
+
+def twin_critic(critic, h, a_dc, a_g, weight_grads: bool):
+    """``critic(h, a_dc, a_g)`` on the HIP kernels of ops/csrc/hip/
+    critic_mlp.hpp, differentiable in ``h`` and, with ``weight_grads``, in the
+    critic's parameters (their gradients reach ``.grad`` by autograd's own
+    accumulation).  Without it the weights are passed detached and the
+    weight-gradient kernel is not launched."""
+    weights = []
+    for lin in critic_linears(critic):
+        weights += [lin.weight, lin.bias]
+    if not weight_grads:
+        weights = [w.detach() for w in weights]
+    return _TwinCritic.apply(h.float().contiguous(), a_dc.long().contiguous(),
+                             a_g.long().contiguous(), critic.n_dc, critic.n_g,
+                             *weights)

@@ -47,7 +47,7 @@ class MaskedHybridSAC(nn.Module):
                  critic: TwinQuantileCritic, n_quantiles: int = 32,
                  alpha: float = 0.2, actor_lr: float = 3e-4, critic_lr: float = 3e-4,
                  device: Optional[torch.device] = None, capturable: bool = False,
-                 fused_critic: bool = False):
+                 fused_critic: bool = False, fused_critic_mlp: bool = False):
         super().__init__()
         self.encoder, self.actor, self.critic = encoder, actor, critic
         self.target_critic = TwinQuantileCritic(encoder.out_dim, actor.n_dc,
@@ -76,6 +76,27 @@ class MaskedHybridSAC(nn.Module):
         # cannot serve this agent, warn once and keep the torch path.
         self.fused_critic = bool(fused_critic)
         self._fused_ready: Optional[bool] = None
+        # opt-in HIP twin critic, forward and backward (fused.twin_critic);
+        # independent of fused_critic, same decide-once and fallback rule
+        self.fused_critic_mlp = bool(fused_critic_mlp)
+        self._fused_mlp_ready: Optional[bool] = None
+
+    def _use_fused_mlp(self) -> bool:
+        if not self.fused_critic_mlp:
+            return False
+        if self._fused_mlp_ready is None:
+            why = fused.unusable(self, "twin_critic_fwd")
+            if why is not None:
+                warnings.warn(f"fused_critic_mlp unavailable: {why}; "
+                              "falling back to the torch critic")
+            self._fused_mlp_ready = why is None
+        return self._fused_mlp_ready
+
+    def _q(self, h, a_dc, a_g, weight_grads: bool):
+        """critic(h, a_dc, a_g), on the HIP kernels when the flag is on."""
+        if self._use_fused_mlp():
+            return fused.twin_critic(self.critic, h, a_dc, a_g, weight_grads)
+        return self.critic(h, a_dc, a_g)
 
     def _use_fused(self) -> bool:
         if not self.fused_critic:
@@ -134,19 +155,25 @@ class MaskedHybridSAC(nn.Module):
     def _critic_phase(self, s, s_next, a_dc, a_g, r_eff, done, gamma,
                       mask_dc_n, mask_g_n):
         """QR-Huber TD loss against entropy-regularized target quantiles."""
-        h = self.encoder(s)
+        if self._use_fused_mlp():
+            # no graph through the encoder: critic_opt holds no encoder
+            # parameter and actor_opt.zero_grad drops its .grad unread
+            with torch.no_grad():
+                h = self.encoder(s)
+        else:
+            h = self.encoder(s)
         taus = self.taus.to(self.device)
         if self._use_fused():
             target = fused.td_target(self, s_next, mask_dc_n, mask_g_n,
                                      r_eff, done, gamma)
-            q1, q2 = self.critic(h, a_dc, a_g)
+            q1, q2 = self._q(h, a_dc, a_g, True)
             loss = fused.qr_huber_twin(q1, q2, target, taus)
         else:
             h_next = self.encoder(s_next).detach()
             with torch.no_grad():
                 q_next, _ = self._target_quantiles(h_next, mask_dc_n, mask_g_n)
                 target = (r_eff + (1 - done) * gamma * q_next).detach()
-            q1, q2 = self.critic(h, a_dc, a_g)
+            q1, q2 = self._q(h, a_dc, a_g, True)
             loss = quantile_huber_loss(q1, target, taus) + \
                 quantile_huber_loss(q2, target, taus)
         self._optimize(self.critic_opt, loss, list(self.critic.parameters()))
@@ -160,7 +187,9 @@ class MaskedHybridSAC(nn.Module):
         a_dc_pi, logp_dc = sample_categorical(logits_dc, mask_dc)
         a_g_pi, logp_g = sample_categorical(logits_g, mask_g)
         logp = logp_dc + logp_g
-        q1_pi, q2_pi = self.critic(h_pi, a_dc_pi, a_g_pi)
+        # no critic weight gradients here: actor_opt holds no critic parameter
+        # and the next critic_opt.zero_grad drops them unread
+        q1_pi, q2_pi = self._q(h_pi, a_dc_pi, a_g_pi, False)
         q_pi = torch.min(q1_pi, q2_pi).mean(dim=-1)
         actor_loss = (self.alpha.detach() * logp - q_pi).mean()
         temp_loss = -(self.log_alpha * (logp.detach() + target_entropy)).mean()

@@ -147,6 +147,10 @@ def parse_args(argv=None):
     p.add_argument("--rl-target-ups", type=float, default=180.0,
                    help="chsac_af batched engine: SAC update-rate target for "
                         "the overlapped loop (<=0 = pure-throughput mode).")
+    p.add_argument("--rl-fused-critic-mlp", action="store_true", default=False,
+                   help="chsac_af batched engine: run the twin critic's forward "
+                        "and backward as HIP kernels (falls back to torch with "
+                        "a warning if they cannot serve the agent).")
     p.add_argument("--rl-fused-critic", action="store_true", default=False,
                    help="chsac_af batched engine: run the SAC critic phase's "
                         "TD target and quantile-Huber loss as fused HIP "
@@ -287,6 +291,7 @@ def main(argv=None):
                             rl_exact_p99=args.rl_exact_p99,
                             rl_target_updates_per_s=args.rl_target_ups,
                             rl_fused_critic=args.rl_fused_critic,
+                            rl_fused_critic_mlp=args.rl_fused_critic_mlp,
                             fp32_coeff_eval=args.fp32_coeff_eval,
                             pop_series=args.pop_series > 0,
                             pop_series_every=max(1, args.pop_series),

@@ -1,16 +1,18 @@
-"""Graph-replayed SAC step rate with the fused critic phase off and on, and
-the isolated time of each fused kernel against the torch code it replaces.
+"""Graph-replayed SAC step rate with the fused critic phase off ("off"), on
+("on") and on together with the HIP twin critic ("mlp": fused_critic +
+fused_critic_mlp), and the isolated time of each fused kernel against the
+torch code it replaces.
 
-Same agent, ring and batch as bench.py::measure_rl_steps_per_sec.  Both
+Same agent, ring and batch as bench.py::measure_rl_steps_per_sec.  All
 steppers live in one process and are timed in alternation (--repeats windows
 of --steps replays each, after --warmup replays), so drift on a shared host
-hits both alike; the spread printed is min..max over the windows.
+hits all alike; the spread printed is min..max over the windows.
 
     python scripts/gpu_sac_step_perf.py [--steps 300] [--repeats 7]
 
 Prints one JSON line.  For per-step kernel counts run it once per mode under
 ``rocprofv3 --kernel-trace --stats -- python scripts/gpu_sac_step_perf.py
---only off|on --repeats 1`` and divide the call counts by the replays."""
+--only off|on|mlp --repeats 1`` and divide the call counts by the replays."""
 import argparse
 import json
 import os
@@ -32,12 +34,13 @@ from distributed_cluster_gpus_amd.rl.sac import quantile_huber_loss  # noqa: E40
 OBS, BATCH = 49, 256
 
 
-def make_stepper(fused_critic):
+def make_stepper(fused_critic, fused_critic_mlp=False):
     torch.manual_seed(0)
     agent = CHSACAgent(CHSACAgentConfig(
         obs_dim=OBS, n_dc=8, n_g_choices=8,
         constraints={"latency_p99": 500.0, "gpu_over": 0.0}, device="cuda",
-        graph_capturable=True, fused_critic=fused_critic))
+        graph_capturable=True, fused_critic=fused_critic,
+        fused_critic_mlp=fused_critic_mlp))
     ring = ReplayRing(capacity=4096, obs_dim=OBS, n_costs=2,
                       cost_names=["latency_p99", "gpu_over"], n_dc=8, n_g=8,
                       device="cuda", seed=0)
@@ -51,6 +54,8 @@ def make_stepper(fused_critic):
         raise RuntimeError(f"capture failed: {step.capture_error}")
     if fused_critic and not agent.algo._fused_ready:
         raise RuntimeError("the fused critic phase fell back to torch")
+    if fused_critic_mlp and not agent.algo._fused_mlp_ready:
+        raise RuntimeError("the HIP twin critic fell back to torch")
     return step
 
 
@@ -113,12 +118,12 @@ def main(argv=None):
     p.add_argument("--steps", type=int, default=300)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--repeats", type=int, default=7)
-    p.add_argument("--only", choices=["off", "on"], default=None)
+    p.add_argument("--only", choices=["off", "on", "mlp"], default=None)
     args = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
-    modes = [m for m in ("off", "on") if args.only in (None, m)]
-    steppers = {m: make_stepper(m == "on") for m in modes}
+    modes = [m for m in ("off", "on", "mlp") if args.only in (None, m)]
+    steppers = {m: make_stepper(m != "off", m == "mlp") for m in modes}
     for s in steppers.values():
         window(s, args.warmup)
     rates = {m: [] for m in modes}
@@ -134,6 +139,9 @@ def main(argv=None):
     if args.only is None:
         out["speedup_median"] = round(out["steps_per_s_on"]["median"] /
                                       out["steps_per_s_off"]["median"], 3)
+        out["speedup_mlp_over_on_median"] = round(
+            out["steps_per_s_mlp"]["median"] /
+            out["steps_per_s_on"]["median"], 3)
         out.update({k: round(v, 1) for k, v in
                     isolated(steppers["on"].agent.algo).items()})
     print(json.dumps(out))
