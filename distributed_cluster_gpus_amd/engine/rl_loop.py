@@ -72,10 +72,16 @@ def make_learner(obs_dim, n_dc, n_g, device, *, world, seed, buffer,
 
 class ServingWeights:
     """The served actor's seven Linear layers laid out in one flat float
-    buffer: per layer the weight transposed to [in][out], then the bias."""
+    buffer: per layer the weight transposed to [in][out], then the bias.
 
-    def __init__(self, agent, buf, obs_dim, n_dc, n_g, hid):
-        if not self.servable(agent, obs_dim, n_dc, n_g, hid):
+    ``engine_limits=False`` packs any actor of the seven-layer shape, up to
+    the wider limits of ``rl_forward_mfma`` (which checks them itself); the
+    advance kernel's own limits are what ``servable`` adds."""
+
+    def __init__(self, agent, buf, obs_dim, n_dc, n_g, hid, *,
+                 engine_limits=True):
+        fits = self.servable if engine_limits else self.has_layout
+        if not fits(agent, obs_dim, n_dc, n_g, hid):
             raise ValueError("agent's actor does not fit the serving layout")
         # (buffer-slice view, source parameter) pairs, so each refresh is a
         # handful of small device-to-device copies
@@ -100,7 +106,7 @@ class ServingWeights:
                 agent.actor.head_g[0], agent.actor.head_g[2]]
 
     @classmethod
-    def servable(cls, agent, obs_dim, n_dc, n_g, hid) -> bool:
+    def has_layout(cls, agent, obs_dim, n_dc, n_g, hid) -> bool:
         try:
             shapes = [tuple(l.weight.shape) for l in cls.linears(agent)]
         except (AttributeError, IndexError, TypeError):
@@ -108,7 +114,12 @@ class ServingWeights:
         H = hid
         want = [(H, obs_dim), (H, H), (H, H),
                 (H, H), (n_dc, H), (H, H), (n_g, H)]
-        return shapes == want and n_dc <= 8 and n_g <= 8 and obs_dim <= 64
+        return shapes == want
+
+    @classmethod
+    def servable(cls, agent, obs_dim, n_dc, n_g, hid) -> bool:
+        return cls.has_layout(agent, obs_dim, n_dc, n_g, hid) and \
+            n_dc <= 8 and n_g <= 8 and obs_dim <= 64
 
     @torch.no_grad()
     def refresh(self):

@@ -1,6 +1,6 @@
 // Test-only entry points of the replica-engine extensions: stand-alone
-// drivers that run the production device functions (in-kernel actor forward,
-// subgroup reductions, Philox draws, analytic models, grid searches) on given
+// drivers that run the production device functions (in-kernel actor forward
+// and action pick, subgroup reductions, Philox draws, analytic models, grid searches) on given
 // inputs, with their kernels, host wrappers and bindings.  Not a stand-alone
 // header: replica_engine.hip includes it after the device code it drives.
 #pragma once
@@ -36,10 +36,14 @@ std::vector<torch::Tensor> rl_forward_debug(torch::Tensor pw,
                                             torch::Tensor obs,
                                             int64_t hid, int64_t n_dc,
                                             int64_t n_g) {
-  TORCH_CHECK(pw.is_cuda() && obs.is_cuda() && pw.dtype() == torch::kFloat32);
+  // the slot's LDS rows: RL_MAX_OBS, RL_MAX_HID, and the g logits at +8 of
+  // the RL_MAX_LOG-float logits row
+  check_rl_forward_args("rl_forward_debug", pw, obs, hid, n_dc, n_g, 1,
+                        RL_MAX_OBS, RL_MAX_HID, RL_MAX_LOG / 2);
   int B = obs.size(0), D = obs.size(1);
   auto out_dc = torch::empty({B, n_dc}, obs.options());
   auto out_g = torch::empty({B, n_g}, obs.options());
+  if (B == 0) return {out_dc, out_g};
   int rpb = REPLICAS_PER_BLOCK;
   int blocks = (B + rpb - 1) / rpb;
   size_t shmem = (size_t)rpb * RL_LDS_BYTES;
@@ -51,6 +55,63 @@ std::vector<torch::Tensor> rl_forward_debug(torch::Tensor pw,
                      out_g.data_ptr<float>());
   check_launch("rl_forward_kernel");
   return {out_dc, out_g};
+}
+
+// standalone masked Gumbel-max pick (test/verification path): one subgroup
+// per row runs the production rl_pick_pure from a fresh state at (key, ctr);
+// lane 0 writes the action and the counter the pick leaves behind
+__global__ void __launch_bounds__(THREADS_PER_BLOCK)
+rl_pick_debug_kernel(const float* logits, const int* mask,
+                     const int64_t* keys, const int64_t* ctrs, int64_t B,
+                     int n, int det, int* action, int64_t* ctr_after) {
+  int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / SUBW;
+  int lane = threadIdx.x & (SUBW - 1);
+  if (row >= B) return;  // whole subgroups leave together
+  PhiloxState st{(uint64_t)keys[row], (uint64_t)ctrs[row]};
+  int a = rl_pick_pure(logits + row * n, mask[row], n, det, st);
+  if (lane == 0) {
+    action[row] = a;
+    ctr_after[row] = (int64_t)st.ctr;
+  }
+}
+
+std::vector<torch::Tensor> rl_pick_debug(torch::Tensor logits,
+                                         torch::Tensor mask,
+                                         torch::Tensor key, torch::Tensor ctr,
+                                         bool det) {
+  TORCH_CHECK(logits.is_cuda() && mask.is_cuda() && key.is_cuda() &&
+                  ctr.is_cuda() && mask.device() == logits.device() &&
+                  key.device() == logits.device() &&
+                  ctr.device() == logits.device(),
+              "rl_pick_debug: all tensors must be on one GPU");
+  TORCH_CHECK(logits.dtype() == torch::kFloat32 &&
+                  mask.dtype() == torch::kInt32 &&
+                  key.dtype() == torch::kInt64 && ctr.dtype() == torch::kInt64,
+              "rl_pick_debug: logits f32, mask i32, key i64, ctr i64");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 8,
+              "rl_pick_debug: logits must be [B, n] with 1 <= n <= 8");
+  int64_t B = logits.size(0);
+  TORCH_CHECK(mask.dim() == 1 && mask.size(0) == B && key.sizes() == mask.sizes()
+                  && ctr.sizes() == mask.sizes(),
+              "rl_pick_debug: mask, key and ctr must be [B]");
+  TORCH_CHECK(B < (int64_t(1) << 24), "rl_pick_debug: B is too large");
+  logits = logits.contiguous();
+  mask = mask.contiguous();
+  key = key.contiguous();
+  ctr = ctr.contiguous();
+  auto action = torch::empty({B}, mask.options());
+  auto ctr_after = torch::empty({B}, ctr.options());
+  if (B == 0) return {action, ctr_after};
+  hipStream_t stream = at::hip::getCurrentHIPStream();
+  const int64_t rpb = REPLICAS_PER_BLOCK;
+  hipLaunchKernelGGL(rl_pick_debug_kernel, dim3((unsigned)((B + rpb - 1) / rpb)),
+                     dim3(THREADS_PER_BLOCK), 0, stream,
+                     logits.data_ptr<float>(), mask.data_ptr<int>(),
+                     key.data_ptr<int64_t>(), ctr.data_ptr<int64_t>(), B,
+                     (int)logits.size(1), det ? 1 : 0, action.data_ptr<int>(),
+                     ctr_after.data_ptr<int64_t>());
+  check_launch("rl_pick_debug_kernel");
+  return {action, ctr_after};
 }
 
 // standalone drivers for the subgroup reduction helpers (test/verification
@@ -491,6 +552,14 @@ inline void bind_debug_entries(py::module_& m) {
         "(pw, obs[B,D], hid, n_dc, n_g) -> (logits_dc, logits_g)",
         py::arg("pw"), py::arg("obs"), py::arg("hid"), py::arg("n_dc"),
         py::arg("n_g"));
+  // rows (rl_forward_debug, rl_pick_debug) one workgroup of this build takes
+  m.attr("DEBUG_ROWS_PER_BLOCK") = (int)REPLICAS_PER_BLOCK;
+  m.def("rl_pick_debug", &dcg::rl_pick_debug,
+        "production masked Gumbel-max pick, one subgroup per row from a fresh "
+        "state at (key, ctr): (logits[B,n] f32, mask[B] i32, key[B] i64, "
+        "ctr[B] i64, det) -> (action[B] i32, ctr_after[B] i64)",
+        py::arg("logits"), py::arg("mask"), py::arg("key"), py::arg("ctr"),
+        py::arg("det"));
   m.def("wave_reduce_debug", &dcg::wave_reduce_debug,
         "production wave_argmin_f64 / wave_argmin_idx_f64 over each row of "
         "(vals[B,64] f64, idx[B,64] i32) -> (value, lane, value, index)",

@@ -999,27 +999,36 @@ __device__ __forceinline__ double u01_at(uint64_t key, uint64_t ctr) {
 // path's log_softmax+Gumbel argmax: the log-softmax shift cancels in the
 // argmax).  mask==0 falls back to all-valid, mirroring the host guard.
 // Wave-uniform: every lane computes the same winner from the same draws.
-__device__ int rl_pick(Ctx& c, const float* logits, int mask, int n) {
-  const EngineDesc& S = *c.S;
+// The pick itself knows nothing of the replica context, so that the test
+// entry rl_pick_debug (debug_entries.hpp) runs the very function the advance
+// kernel inlines.  It takes n counters whatever the mask admits (category j
+// draws at ctr0 + j) and none in deterministic mode.
+__device__ __forceinline__ int rl_pick_pure(const float* logits, int mask,
+                                            int n, int det,
+                                            PhiloxState& rng) {
   if (mask == 0) mask = (1 << n) - 1;
   double best = -D_INF;
   int arg = 0;
-  if (S.rl_det) {
+  if (det) {
     for (int j = 0; j < n; ++j) {
       double z = logits[j];
       if ((mask >> j & 1) && z > best) { best = z; arg = j; }
     }
     return arg;
   }
-  uint64_t ctr0 = c.rng.ctr;
-  c.rng.ctr += n;
+  uint64_t ctr0 = rng.ctr;
+  rng.ctr += n;
   for (int j = 0; j < n; ++j) {
     if (!(mask >> j & 1)) continue;
-    double u = fmax(u01_at(c.rng.key, ctr0 + j), 1e-20);
+    double u = fmax(u01_at(rng.key, ctr0 + j), 1e-20);
     double z = (double)logits[j] - log(-log(u));
     if (z > best) { best = z; arg = j; }
   }
   return arg;
+}
+
+__device__ int rl_pick(Ctx& c, const float* logits, int mask, int n) {
+  return rl_pick_pure(logits, mask, n, c.S->rl_det, c.rng);
 }
 
 // build obs+masks into LDS, run the actor, sample (a_dc, a_g)
@@ -2112,16 +2121,61 @@ rl_forward_mfma_kernel(const float* pw, const float* obs, int B, int obs_dim,
   }
 }
 
+// floats in the flat actor-weights buffer (EngineDesc::pw) at these dims
+inline int64_t rl_pw_numel(int64_t obs_dim, int64_t hid, int64_t n_dc,
+                           int64_t n_g) {
+  const int64_t H = hid;
+  return (obs_dim * H + H) + 2 * (H * H + H) + (H * H + H) +
+         (H * n_dc + n_dc) + (H * H + H) + (H * n_g + n_g);
+}
+
+// What both actor-forward entries (rl_forward_mfma here, rl_forward_debug in
+// debug_entries.hpp) ask of their arguments before they launch: the kernels
+// index pw by the layout alone and keep obs_dim, hid and the head widths in
+// fixed LDS rows, so a short buffer or a dimension past its row reads or
+// writes out of bounds.
+inline void check_rl_forward_args(const char* who, const torch::Tensor& pw,
+                                  const torch::Tensor& obs, int64_t hid,
+                                  int64_t n_dc, int64_t n_g, int64_t min_hid,
+                                  int64_t max_obs, int64_t max_hid,
+                                  int64_t max_n) {
+  TORCH_CHECK(pw.is_cuda() && pw.dtype() == torch::kFloat32 &&
+                  pw.is_contiguous(),
+              who, ": pw must be a contiguous float32 tensor on the GPU");
+  TORCH_CHECK(obs.dim() == 2, who, ": obs must be [B, obs_dim], got ",
+              obs.dim(), " dimension(s)");
+  TORCH_CHECK(obs.dtype() == torch::kFloat32 && obs.is_contiguous() &&
+                  obs.device() == pw.device(),
+              who, ": obs must be contiguous float32 on pw's device");
+  TORCH_CHECK(obs.size(0) < (int64_t(1) << 24), who, ": B = ", obs.size(0),
+              " is too large");
+  const int64_t D = obs.size(1);
+  TORCH_CHECK(D >= 1 && D <= max_obs, who, ": obs_dim = ", D,
+              " outside [1, ", max_obs, "]");
+  TORCH_CHECK(hid >= min_hid && hid <= max_hid, who, ": hid = ", hid,
+              " outside [", min_hid, ", ", max_hid, "]");
+  TORCH_CHECK(n_dc >= 1 && n_dc <= max_n && n_g >= 1 && n_g <= max_n, who,
+              ": n_dc = ", n_dc, ", n_g = ", n_g, " outside [1, ", max_n, "]");
+  TORCH_CHECK(pw.numel() == rl_pw_numel(D, hid, n_dc, n_g), who, ": pw holds ",
+              pw.numel(), " floats, the layout at obs_dim = ", D, ", hid = ",
+              hid, ", n_dc = ", n_dc, ", n_g = ", n_g, " takes ",
+              rl_pw_numel(D, hid, n_dc, n_g));
+}
+
 std::vector<torch::Tensor> rl_forward_mfma(torch::Tensor pw,
                                            torch::Tensor obs,
                                            int64_t hid, int64_t n_dc,
                                            int64_t n_g) {
-  TORCH_CHECK(pw.is_cuda() && obs.is_cuda() && pw.dtype() == torch::kFloat32
-              && obs.dtype() == torch::kFloat32 && obs.is_contiguous());
-  TORCH_CHECK(hid % 16 == 0 && hid <= 256 && n_dc <= 16 && n_g <= 16);
+  // obs_dim and hid each fill one LDS row of MF_STRIDE floats; 16 waves give
+  // 16 column tiles, and the head tiles take 16 actions
+  check_rl_forward_args("rl_forward_mfma", pw, obs, hid, n_dc, n_g, 16,
+                        MF_STRIDE - 1, 256, 16);
+  TORCH_CHECK(hid % 16 == 0, "rl_forward_mfma: hid = ", hid,
+              " is no multiple of 16");
   int B = obs.size(0), D = obs.size(1);
   auto out_dc = torch::empty({B, n_dc}, obs.options());
   auto out_g = torch::empty({B, n_g}, obs.options());
+  if (B == 0) return {out_dc, out_g};
   int blocks = (B + 15) / 16;
   hipStream_t stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(rl_forward_mfma_kernel, dim3(blocks), dim3(1024), 0,
@@ -2333,10 +2387,7 @@ class BatchedSimHip {
     }
     if (S_.serve_device) {
       // the seven layers of EngineDesc::pw
-      const int64_t H = S_.hid, G = S_.n_g;
-      bind(S_.pw, "policy_weights",
-           (O * H + H) + 2 * (H * H + H) + (H * H + H) + (H * D + D) +
-               (H * H + H) + (H * G + G));
+      bind(S_.pw, "policy_weights", rl_pw_numel(O, S_.hid, D, S_.n_g));
     }
     if (S_.algo == A_CHSAC) {
       const int64_t PP = S_.pp_cap, TR = S_.tr_cap;

@@ -7,7 +7,15 @@ The mpmath recipes are the formulas as the source writes them, on the same
 f64 inputs and with the same f64 constants (M_PI, 1.0 / 1.8, the engine's
 mu = log(50000) rounded to f64); only the arithmetic and the transcendental
 calls are carried out at 120 bits.  So the measured error is the rounding of
-the recipe's own operations, not of its constants."""
+the recipe's own operations, not of its constants.
+
+The served policy's pick (rl_pick in replica_engine.hip) draws differently
+from the recipes above: a head with n categories takes n counters at once,
+ctr0 .. ctr0 + n - 1 (64-bit, wrapping), whatever its mask; category j's
+uniform is the u01 of the Philox block at ctr0 + j, clamped at 1e-20 from
+below, and its score is logit_j - log(-log u).  The DC head picks first, the
+GPU-count head right after it, so one decision takes n_dc + n_g counters; the
+deterministic mode draws nothing.  pick_reference() below is that recipe."""
 import functools
 import math
 
@@ -231,3 +239,120 @@ def replay_replica(seed, global_id, first_arrivals, arrivals, n_dc, end_time,
         nxt[s] = t + ia
     out.arr_next = nxt
     return out
+
+
+# --------------------------------------------------- the served policy's pick
+
+M64 = 2 ** 64 - 1
+PICK_SEED = 123
+PICK_NS = (1, 3, 5, 8)     # category counts the pick is tested at
+PICK_U_MIN = 1e-20         # the pick clamps its uniform from below here
+
+
+class PickRef:
+    """What the pick must return for one row, and how sure the reference is.
+
+    action, ctr_after: the reference's answer.  Stochastic mode only: `allowed`
+    (category indices the mask admits), `scores` (mpf per category, None where
+    masked out), `tol` and `gap` (reference maximum minus the runner-up's
+    score; inf with one allowed category)."""
+    __slots__ = ("action", "ctr_after", "allowed", "scores", "tol", "gap")
+
+
+def pick_uniform(key, ctr0, j):
+    """Category j's clamped uniform: words 0 and 1 of the block at ctr0 + j."""
+    w = ph.philox4x32(key, (ctr0 + j) & M64)
+    return max(ph.u01_map(w[0], w[1]), PICK_U_MIN)
+
+
+def pick_reference(logits, mask, n, key, ctr, det):
+    """The masked Gumbel-max pick of one row.  `logits`: n floats (float32
+    values); bit j of `mask` admits category j, bits at or above n are
+    ignored, 0 admits all.  The first index wins the argmax.  The counter
+    moves by n whatever the mask, and not at all in deterministic mode.
+
+    tol = 4 * 2**-52 * (1 + |logit| + |g|), the largest over the row's allowed
+    categories, with g = log(-log u), bounds twice the error of one device
+    score.  The device rounds l = log(u) within one ulp, a relative error of
+    at most 2**-52; through the second log that becomes an absolute error of
+    at most 2**-52 (d log x = dx / x), to which the second call adds its own
+    ulp, at most 2**-52 * |g|; the subtraction logit - g rounds once more, by
+    at most 2**-53 * (|logit| + |g|).  One score is therefore off by less than
+    1.5 * 2**-52 * (1 + |logit| + |g|), and the difference of two scores by
+    less than 3 * 2**-52 times the larger such sum; 4 leaves a margin."""
+    ref = PickRef()
+    if mask == 0:
+        mask = (1 << n) - 1
+    ref.allowed = [j for j in range(n) if mask >> j & 1]
+    assert ref.allowed, "no category below n is admitted"
+    if det:
+        ref.action = max(ref.allowed, key=lambda j: (logits[j], -j))
+        ref.ctr_after = ctr
+        return ref
+    ref.ctr_after = (ctr + n) & M64
+    ref.scores = [None] * n
+    ref.tol = 0.0
+    for j in ref.allowed:
+        g = MP.log(-MP.log(MP.mpf(pick_uniform(key, ctr, j))))
+        ref.scores[j] = MP.mpf(float(logits[j])) - g
+        ref.tol = max(ref.tol, 4 * 2.0 ** -52 *
+                      (1 + abs(float(logits[j])) + abs(float(g))))
+    order = sorted(ref.allowed, key=lambda j: (-ref.scores[j], j))
+    ref.action = order[0]
+    ref.gap = math.inf if len(order) == 1 else \
+        float(ref.scores[order[0]] - ref.scores[order[1]])
+    return ref
+
+
+def _pick_key_ctr_rows(rng):
+    """(key, ctr) pairs: the engine's replica keys at counter 0, around the
+    32-bit word boundary (the pick adds j across it) and at the top of the
+    64-bit range, then random ones."""
+    rows = []
+    for g, ctrs in ((0, (0, 2 ** 32 - 1)), (1, (2 ** 32, 2 ** 32 + 1)),
+                    (63, (0, 2 ** 32 - 3)), (2 ** 20, (16, 2 ** 64 - 2))):
+        rows += [(ph.replica_key(PICK_SEED, g), c) for c in ctrs]
+    rnd = rng.integers(0, 2 ** 64, size=(4, 2), dtype=np.uint64)
+    rows += [(int(k), int(c)) for k, c in rnd]
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def pick_rows(n):
+    """The rows the pick is tested on at n categories, as a tuple of
+    (kind, logits float32[n], mask, key, ctr): random and equal logits, under
+    every kind of mask, each at every (key, ctr) pair."""
+    rng = np.random.default_rng(9500 + n)
+    full = (1 << n) - 1
+    rows = []
+    for kc_i, (key, ctr) in enumerate(_pick_key_ctr_rows(rng)):
+        for equal in (False, True):
+            if equal:
+                logits = np.full(n, (0.0, -2.5, 7.25)[kc_i % 3], np.float32)
+            else:
+                logits = (rng.standard_normal(n) * 3).astype(np.float32)
+            masks = [("full", full), ("zero", 0)]
+            masks += [(f"bit{j}", 1 << j) for j in range(n)]
+            masks += [("random", int(rng.integers(1, full + 1)))
+                      for _ in range(4)]
+            if n > 1:
+                masks.append(("without largest",
+                              full & ~(1 << int(np.argmax(logits)))))
+            # bits above n must be ignored (bit 31 would make mask negative:
+            # the engine's masks are bytes, so it is left out)
+            low = int(rng.integers(1, full + 1))
+            masks += [("high bits", low | 1 << n),
+                      ("high bits", low | 1 << (n + 3) | 1 << 30),
+                      ("high bits, full", full | 0x7FFFFF00)]
+            for kind, mask in masks:
+                rows.append((("equal " if equal else "") + kind, logits, mask,
+                             key, ctr))
+    for r in rows:
+        r[1].setflags(write=False)
+    return tuple(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def pick_references(n, det):
+    return tuple(pick_reference(lg, mask, n, key, ctr, det)
+                 for _, lg, mask, key, ctr in pick_rows(n))

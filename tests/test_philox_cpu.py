@@ -2,7 +2,9 @@
 CPU: philox4x32 to the Random123 known-answer vectors, every distribution
 recipe to mpmath at 120 bits on the word rows that test_gpu_rng.py feeds the
 device (tests/rng_reference.py), the seed draw of BatchedEngine to the
-recipes, and the self-conditions of the whole-stream replay.
+recipes, the self-conditions of the whole-stream replay, and the reference of
+the served policy's pick (its draw layout, hand cases, and that no committed
+row is within a rounding of a different action).
 
 Largest error of the host recipes over those rows, in ulps of the result
 (rng_reference.HOST_MAX_ULP, asserted below):
@@ -219,3 +221,100 @@ def test_replay_conditions_hold_for_the_chosen_seed(case):
         assert rep.jid == sum(rep.n_arrivals) == len(rep.jobs) > 500
         per_arrival = 1 if case == "poisson" else 2
         assert rep.ctr >= len(rows[r]) + rep.jid * (per_arrival + 1)
+
+
+# ------------------------------------------------ the served policy's pick
+
+def test_pick_uniform_is_the_u01_of_words_0_and_1():
+    """rl_pick's u01_at writes ((w0 >> 5) * 2**26 + (w1 >> 6)) * 2**-53 of the
+    block at ctr0 + j; the reference takes the same words through u01_map."""
+    key = ph.replica_key(R.PICK_SEED, 63)
+    for ctr0 in (0, 2 ** 32 - 1, 2 ** 64 - 2):
+        for j in range(8):
+            c = (ctr0 + j) % 2 ** 64
+            w = ph.philox4x32(key, c)
+            u = R.pick_uniform(key, ctr0, j)
+            assert Fraction(u) == Fraction((w[0] >> 5) * 2 ** 26 + (w[1] >> 6),
+                                           2 ** 53)
+            assert u == ph.philox_u01(key, c) == ph.u01_map(w[0], w[1])
+        # distinct counters, distinct draws
+        assert len({R.pick_uniform(key, ctr0, j) for j in range(8)}) == 8
+    # the clamp is the recipe's, not Philox's: it only acts on u = 0
+    assert R.PICK_U_MIN == 1e-20 and max(0.0, R.PICK_U_MIN) == 1e-20
+
+
+def test_pick_reference_by_hand():
+    key = ph.replica_key(R.PICK_SEED, 1)
+    lg = [0.5, 2.0, 2.0, -1.0, 2.0]
+    det = lambda mask, n=5: R.pick_reference(lg, mask, n, key, 40, True)  # noqa: E731
+    assert det(0b11111).action == 1            # first of the tied largest
+    assert det(0).action == 1                  # zero mask: all valid
+    assert det(0b11101).action == 2
+    assert det(0b10001).action == 4
+    assert det(0b01001).action == 0
+    assert det(0b01000).action == 3
+    assert det(0b11111 | 1 << 5 | 1 << 30).action == 1   # bits above n
+    assert det(0b100 | 1 << 3, n=3).action == 2          # bit 3 is above n = 3
+    assert det(0b11111).ctr_after == 40        # no draw
+    # stochastic: n counters whatever the mask, argmax of logit - log(-log u)
+    for mask in (0, 0b11111, 0b00100, 0b01010):
+        ref = R.pick_reference(lg, mask, 5, key, 2 ** 32 - 2, False)
+        assert ref.ctr_after == 2 ** 32 + 3
+        allowed = [j for j in range(5) if (mask or 31) >> j & 1]
+        assert ref.allowed == allowed
+        z = {j: lg[j] - math.log(-math.log(ph.philox_u01(key, 2 ** 32 - 2 + j)))
+             for j in allowed}
+        assert ref.action == max(allowed, key=lambda j: z[j])
+        assert all((ref.scores[j] is None) == (j not in allowed)
+                   for j in range(5))
+        assert all(abs(float(ref.scores[j]) - z[j]) <= ref.tol for j in allowed)
+    assert R.pick_reference(lg, 0b00100, 5, key, 7, False).gap == math.inf
+    assert R.pick_reference(lg, 1, 1, key, 2 ** 64 - 1, False).ctr_after == 0
+    # u = 0 is clamped, so the score stays finite
+    g = R.MP.log(-R.MP.log(R.MP.mpf(R.PICK_U_MIN)))
+    assert 3.82 < float(g) < 3.84
+
+
+@pytest.mark.parametrize("n", R.PICK_NS)
+def test_pick_rows_cover_the_cases_and_none_is_ambiguous(n):
+    """test_gpu_policy_serving.py asserts the device's action equal to the
+    reference's on every row whose two best scores are further apart than
+    tol; here: that is every row, so a device rounding cannot excuse a
+    different action."""
+    rows = R.pick_rows(n)
+    full = (1 << n) - 1
+    kinds = {k for k, *_ in rows}
+    want = {"full", "zero", "random", "high bits", "high bits, full"} | \
+        {f"bit{j}" for j in range(n)} | ({"without largest"} if n > 1 else set())
+    assert kinds == want | {"equal " + k for k in want}
+    ctrs = {c for *_, c in rows}
+    assert {0, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1} <= ctrs
+    assert all(lg.dtype.name == "float32" and lg.shape == (n,)
+               for _, lg, *_ in rows)
+    assert all(0 <= m < 2 ** 31 for _, _, m, *_ in rows)
+    for kind, lg, mask, _, _ in rows:
+        if kind.startswith("equal"):
+            assert len(set(lg.tolist())) == 1
+        if kind.endswith("without largest"):
+            assert not mask >> int(lg.argmax()) & 1 and mask
+        if "high bits" in kind:
+            assert mask & full and mask & ~full
+    sto, det = R.pick_references(n, False), R.pick_references(n, True)
+    inside = [i for i, r in enumerate(sto) if r.gap <= r.tol]
+    print(f"n={n}: {len(rows)} rows, {len(inside)} inside tol, smallest gap "
+          f"{min(r.gap for r in sto):.3g}, largest tol "
+          f"{max(r.tol for r in sto):.3g}")
+    assert inside == []
+    assert max(r.tol for r in sto) < 1e-13
+    for (kind, lg, mask, key, ctr), s, d in zip(rows, sto, det):
+        assert s.action in s.allowed and d.action in d.allowed
+        assert s.ctr_after == (ctr + n) % 2 ** 64 and d.ctr_after == ctr
+        assert d.action == min(j for j in d.allowed
+                               if lg[j] == max(lg[k] for k in d.allowed))
+        if kind.startswith("equal"):
+            assert d.action == d.allowed[0]
+    if n > 1:
+        # the equal-logit rows are decided by the draws: not always the
+        # lowest allowed index
+        assert any(s.action != s.allowed[0] for (k, *_), s in zip(rows, sto)
+                   if k.startswith("equal"))

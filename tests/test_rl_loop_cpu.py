@@ -138,6 +138,30 @@ def test_agents_that_are_not_servable():
                        RL_HID)
 
 
+def test_layout_without_the_engine_limits():
+    """rl_forward_mfma takes wider heads and observations than the advance
+    kernel: such an actor has the layout but is not servable in the engine."""
+    import types
+    nn = torch.nn
+    D, H, n_dc, n_g = 70, 32, 9, 16
+    head = lambda n: nn.Sequential(nn.Linear(H, H), nn.ReLU(),  # noqa: E731
+                                   nn.Linear(H, n))
+    agent = types.SimpleNamespace(
+        encoder=types.SimpleNamespace(net=nn.Sequential(
+            nn.Linear(D, H), nn.ReLU(), nn.Linear(H, H), nn.ReLU(),
+            nn.Linear(H, H), nn.ReLU())),
+        actor=types.SimpleNamespace(head_dc=head(n_dc), head_g=head(n_g)))
+    assert ServingWeights.has_layout(agent, D, n_dc, n_g, H)
+    assert not ServingWeights.has_layout(agent, D, n_dc, n_g - 1, H)
+    assert not ServingWeights.servable(agent, D, n_dc, n_g, H)
+    buf = torch.zeros(policy_weights_numel(D, n_dc, n_g, H))
+    with pytest.raises(ValueError):
+        ServingWeights(agent, buf, D, n_dc, n_g, H)
+    w = ServingWeights(agent, buf, D, n_dc, n_g, H, engine_limits=False)
+    w.refresh()
+    assert torch.equal(buf, torch.cat(_layer_slices(agent)))
+
+
 # ---------------- mask expansion ----------------
 def test_expand_mask():
     m = expand_mask(torch.tensor([0, 1, 0x80, 0xFF], dtype=torch.uint8), 8)
