@@ -174,6 +174,7 @@ class BatchedEngine:
                  rl_target_updates_per_s: float = 180.0,
                  rl_fused_critic: bool = False,
                  rl_fused_critic_mlp: bool = False,
+                 rl_fused_optim: bool = False,
                  tr_cap: int = 262144, arrival_trace=None,
                  subwave: int = 64,
                  pop_series: bool = False, pop_series_every: int = 1,
@@ -253,7 +254,8 @@ class BatchedEngine:
                 buffer=rl_buffer, sla_p99_ms=sla_p99_ms, power_cap=power_cap,
                 energy_budget_j=energy_budget_j, agent=rl_agent,
                 fused_critic=bool(rl_fused_critic),
-                fused_critic_mlp=bool(rl_fused_critic_mlp))
+                fused_critic_mlp=bool(rl_fused_critic_mlp),
+                fused_optim=bool(rl_fused_optim))
             serve_device, mfma_serve = rl_loop.serving_mode(
                 self.rl, obs_dim, n_dc, n_g, RL_HID, rl_serve,
                 bool(rl_deterministic))

@@ -46,6 +46,7 @@
 #include "lat_hist.hpp"
 #include "launch_plan.hpp"
 #include "moments.hpp"
+#include "optim_tail.hpp"
 #include "philox.hpp"
 #include "pop_series.hpp"
 #include "sac_target.hpp"
@@ -2878,5 +2879,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weights"), py::arg("h"), py::arg("a_dc"), py::arg("a_g"),
         py::arg("n_dc"), py::arg("n_g"), py::arg("act"), py::arg("dq1"),
         py::arg("dq2"), py::arg("want_dh"), py::arg("want_dw"));
+  m.def("optim_tail", &dcg::optim_tail,
+        "fused clip_grad_norm_ + Adam step + polyak over up to 32 f32 tensors "
+        "in two launches, in place (params, grads, exp_avgs, exp_avg_sqs, "
+        "steps: 0-dim f32 on the device; targets: [] or one tensor or None "
+        "per param; clipped: which grads enter the norm and are scaled)",
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("steps"), py::arg("targets"),
+        py::arg("clipped"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("max_norm"), py::arg("tau"));
+  m.attr("optim_tail_chunk") = (int)dcg::OT_CHUNK;
   dcg::bind_debug_entries(m);
 }

@@ -37,6 +37,7 @@ class CHSACAgentConfig:
     graph_capturable: bool = False  # Adam capturable state (hipGraph path)
     fused_critic: bool = False  # HIP kernels for the critic phase (rl/fused.py)
     fused_critic_mlp: bool = False  # HIP twin critic, forward and backward
+    fused_optim: bool = False  # HIP clip + Adam + polyak (fused.optim_step)
 
 
 class CHSACAgent:
@@ -53,7 +54,8 @@ class CHSACAgent:
                                     device=self.device,
                                     capturable=cfg.graph_capturable,
                                     fused_critic=cfg.fused_critic,
-                                    fused_critic_mlp=cfg.fused_critic_mlp)
+                                    fused_critic_mlp=cfg.fused_critic_mlp,
+                                    fused_optim=cfg.fused_optim)
         self.cmdp = PIDLagrangian(
             {k: Constraint(name=k, target=v) for k, v in cfg.constraints.items()},
             device=cfg.device)

@@ -17,6 +17,11 @@ runs the twin critic itself in HIP (ops/csrc/hip/critic_mlp.hpp):
 ``twin_critic`` is an autograd Function over a forward kernel that keeps its
 activations, a backward kernel for dz and dh, and a weight-gradient kernel
 that is launched only when the critic's parameters ask for gradients.
+
+``MaskedHybridSAC(fused_optim=True)`` (independent of both) replaces
+``clip_grad_norm_`` + ``Adam.step()`` of each optimizer, and the polyak
+average of the target critic, by ``optim_step``: two launches of
+ops/csrc/hip/optim_tail.hpp per optimizer, on torch's own Adam state.
 """
 from typing import List, Optional
 
@@ -170,3 +175,69 @@ def twin_critic(critic, h, a_dc, a_g, weight_grads: bool):
     return _TwinCritic.apply(h.float().contiguous(), a_dc.long().contiguous(),
                              a_g.long().contiguous(), critic.n_dc, critic.n_g,
                              *weights)
+
+
+# optim_tail's table limit (TORCH_CHECKed again before any launch)
+MAX_OPTIM_TENSORS = 32
+
+
+def optim_unusable(opt) -> Optional[str]:
+    """Why ``optim_step`` cannot stand in for ``opt.step()`` (None: it can).
+    The kernel bumps Adam's step counters on the device, which only a
+    capturable Adam keeps there."""
+    if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
+        return "the optimizer is not a plain Adam with one param group"
+    g = opt.param_groups[0]
+    if g["amsgrad"] or g["weight_decay"] != 0 or g["maximize"] \
+            or not g["capturable"] or g.get("differentiable") \
+            or not isinstance(g["lr"], float):
+        return ("Adam is not the default configuration with capturable=True "
+                "(amsgrad, weight_decay, maximize, differentiable or a "
+                "tensor lr is set)")
+    if len(g["params"]) > MAX_OPTIM_TENSORS:
+        return f"more than {MAX_OPTIM_TENSORS} tensors in one optimizer"
+    if not all(p.dtype == torch.float32 and p.is_contiguous()
+               for p in g["params"]):
+        return "the parameters are not all contiguous f32"
+    return None
+
+
+@torch.no_grad()
+def optim_step(opt, clip_params, max_norm, polyak=None):
+    """``clip_grad_norm_(clip_params, max_norm)`` then ``opt.step()`` then,
+    with ``polyak=(target_params, tau)`` (paired with the group's parameters
+    in order), ``target = (1 - tau) * target + tau * param`` — as one
+    ``optim_tail`` call on the optimizer's own Adam state, so checkpoints stay
+    interchangeable with the torch path.  A parameter without ``.grad`` is
+    skipped as Adam skips it.  ``.grad`` is NOT scaled in place by the clip:
+    nothing reads it afterwards, the next ``zero_grad(set_to_none=True)``
+    drops it."""
+    group = opt.param_groups[0]
+    clip_ids = {id(p) for p in clip_params}
+    targets, tau = polyak if polyak is not None else (None, 0.0)
+    P, G, M, V, S, T, C = [], [], [], [], [], [], []
+    for k, p in enumerate(group["params"]):
+        if p.grad is None:
+            if targets is not None:  # no step, but the target still follows
+                targets[k].mul_(1 - tau).add_(tau * p)
+            continue
+        st = opt.state[p]
+        if len(st) == 0:  # as Adam._init_group does for capturable=True
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(
+                p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(
+                p, memory_format=torch.preserve_format)
+        P.append(p)
+        G.append(p.grad)
+        M.append(st["exp_avg"])
+        V.append(st["exp_avg_sq"])
+        S.append(st["step"])
+        T.append(None if targets is None else targets[k])
+        C.append(id(p) in clip_ids)
+    if not P:
+        return
+    beta1, beta2 = group["betas"]
+    _mod().optim_tail(P, G, M, V, S, T if targets is not None else [], C,
+                      group["lr"], beta1, beta2, group["eps"],
+                      float(max_norm), float(tau))

@@ -47,7 +47,8 @@ class MaskedHybridSAC(nn.Module):
                  critic: TwinQuantileCritic, n_quantiles: int = 32,
                  alpha: float = 0.2, actor_lr: float = 3e-4, critic_lr: float = 3e-4,
                  device: Optional[torch.device] = None, capturable: bool = False,
-                 fused_critic: bool = False, fused_critic_mlp: bool = False):
+                 fused_critic: bool = False, fused_critic_mlp: bool = False,
+                 fused_optim: bool = False):
         super().__init__()
         self.encoder, self.actor, self.critic = encoder, actor, critic
         self.target_critic = TwinQuantileCritic(encoder.out_dim, actor.n_dc,
@@ -80,6 +81,24 @@ class MaskedHybridSAC(nn.Module):
         # independent of fused_critic, same decide-once and fallback rule
         self.fused_critic_mlp = bool(fused_critic_mlp)
         self._fused_mlp_ready: Optional[bool] = None
+        # opt-in HIP optimizer tail (fused.optim_step): gradient clip, Adam
+        # and polyak in two launches per optimizer; independent of both
+        # flags above, same decide-once and fallback rule
+        self.fused_optim = bool(fused_optim)
+        self._fused_optim_ready: Optional[bool] = None
+
+    def _use_fused_optim(self) -> bool:
+        if not self.fused_optim:
+            return False
+        if self._fused_optim_ready is None:
+            why = fused.unusable(self, "optim_tail") \
+                or fused.optim_unusable(self.actor_opt) \
+                or fused.optim_unusable(self.critic_opt)
+            if why is not None:
+                warnings.warn(f"fused_optim unavailable: {why}; "
+                              "falling back to the torch optimizer step")
+            self._fused_optim_ready = why is None
+        return self._fused_optim_ready
 
     def _use_fused_mlp(self) -> bool:
         if not self.fused_critic_mlp:
@@ -141,20 +160,30 @@ class MaskedHybridSAC(nn.Module):
         q_min = q_min - self.alpha.detach().to(self.device).view(1,) * logp_n.view(-1, 1)
         return q_min, logp_n
 
-    def _optimize(self, opt, loss, sync_params, clip_params=None):
+    def _optimize(self, opt, loss, sync_params, clip_params=None,
+                  polyak=None):
         """backward -> (optional DP grad all-reduce over sync_params) ->
         clip(5.0) over clip_params (defaults to sync_params; the temperature
-        scalar is synced but never clipped) -> step."""
+        scalar is synced but never clipped) -> step.  ``polyak`` =
+        (target_params, tau) is honoured on the fused_optim path only, where
+        the same launch also moves the targets."""
         opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.allreduce_hook is not None:
             self.allreduce_hook(sync_params)
+        if self._use_fused_optim():
+            fused.optim_step(opt, clip_params or sync_params, 5.0, polyak)
+            return
         nn.utils.clip_grad_norm_(clip_params or sync_params, 5.0)
         opt.step()
 
     def _critic_phase(self, s, s_next, a_dc, a_g, r_eff, done, gamma,
-                      mask_dc_n, mask_g_n):
-        """QR-Huber TD loss against entropy-regularized target quantiles."""
+                      mask_dc_n, mask_g_n, polyak_tau=None):
+        """QR-Huber TD loss against entropy-regularized target quantiles.
+        With ``polyak_tau`` (fused_optim path) the critic's optimizer launch
+        also moves the target critic: the target is read only by the TD
+        target above, and the critic does not change in the actor phase, so
+        this equals polyak at the end of ``update``."""
         if self._use_fused_mlp():
             # no graph through the encoder: critic_opt holds no encoder
             # parameter and actor_opt.zero_grad drops its .grad unread
@@ -176,7 +205,11 @@ class MaskedHybridSAC(nn.Module):
             q1, q2 = self._q(h, a_dc, a_g, True)
             loss = quantile_huber_loss(q1, target, taus) + \
                 quantile_huber_loss(q2, target, taus)
-        self._optimize(self.critic_opt, loss, list(self.critic.parameters()))
+        polyak = None
+        if polyak_tau is not None:
+            polyak = (list(self.target_critic.parameters()), polyak_tau)
+        self._optimize(self.critic_opt, loss, list(self.critic.parameters()),
+                       polyak=polyak)
         return loss
 
     def _actor_phase(self, s, mask_dc, mask_g, target_entropy):
@@ -215,15 +248,18 @@ class MaskedHybridSAC(nn.Module):
             m = batch.get(key, default)
             return m.to(dev).bool() if m is not None else None
 
+        fused_tail = self._use_fused_optim()
         loss_critic = self._critic_phase(
             s, batch["s_next"].to(dev), batch["a_dc"].to(dev),
             batch["a_g"].to(dev), batch["r_eff"].to(dev).unsqueeze(-1),
             batch["done"].to(dev).unsqueeze(-1), gamma,
             _m("mask_dc_n", batch.get("mask_dc")),
-            _m("mask_g_n", batch.get("mask_g")))
+            _m("mask_g_n", batch.get("mask_g")),
+            polyak_tau=tau if fused_tail else None)
         actor_loss, temp_loss = self._actor_phase(
             s, _m("mask_dc"), _m("mask_g"), target_entropy)
-        self._polyak(tau)
+        if not fused_tail:
+            self._polyak(tau)
 
         if not compute_stats:
             return {}

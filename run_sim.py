@@ -151,6 +151,11 @@ def parse_args(argv=None):
                    help="chsac_af batched engine: run the twin critic's forward "
                         "and backward as HIP kernels (falls back to torch with "
                         "a warning if they cannot serve the agent).")
+    p.add_argument("--rl-fused-optim", action="store_true", default=False,
+                   help="chsac_af batched engine: run gradient clip, Adam step "
+                        "and polyak of each SAC optimizer step as two HIP "
+                        "kernels (falls back to torch with a warning if they "
+                        "cannot serve the agent).")
     p.add_argument("--rl-fused-critic", action="store_true", default=False,
                    help="chsac_af batched engine: run the SAC critic phase's "
                         "TD target and quantile-Huber loss as fused HIP "
@@ -292,6 +297,7 @@ def main(argv=None):
                             rl_target_updates_per_s=args.rl_target_ups,
                             rl_fused_critic=args.rl_fused_critic,
                             rl_fused_critic_mlp=args.rl_fused_critic_mlp,
+                            rl_fused_optim=args.rl_fused_optim,
                             fp32_coeff_eval=args.fp32_coeff_eval,
                             pop_series=args.pop_series > 0,
                             pop_series_every=max(1, args.pop_series),

@@ -37,6 +37,8 @@ def main(argv=None):
                    help="fused HIP kernels for the SAC critic phase")
     p.add_argument("--fused-critic-mlp", action="store_true", default=False,
                    help="HIP kernels for the twin critic's forward and backward")
+    p.add_argument("--fused-optim", action="store_true", default=False,
+                   help="HIP kernels for gradient clip, Adam step and polyak")
     p.add_argument("--checkpoint", type=str, default="chsac_dp.pt")
     p.add_argument("--replay-npz", type=str, default=None,
                    help="also dump the replay ring as an offline .npz dataset")
@@ -66,7 +68,8 @@ def main(argv=None):
                         rl_warmup=args.warmup, rl_batch=args.batch,
                         rl_train_interval=args.train_interval,
                         rl_fused_critic=args.fused_critic,
-                        rl_fused_critic_mlp=args.fused_critic_mlp)
+                        rl_fused_critic_mlp=args.fused_critic_mlp,
+                        rl_fused_optim=args.fused_optim)
     # replicate the agent across ranks, then train data-parallel
     for mod in (eng.rl.encoder, eng.rl.actor, eng.rl.critic,
                 eng.rl.algo.target_critic):
