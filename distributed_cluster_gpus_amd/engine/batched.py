@@ -175,6 +175,7 @@ class BatchedEngine:
                  rl_fused_critic: bool = False,
                  rl_fused_critic_mlp: bool = False,
                  rl_fused_optim: bool = False,
+                 rl_fused_actor_heads: bool = False,
                  tr_cap: int = 262144, arrival_trace=None,
                  subwave: int = 64,
                  pop_series: bool = False, pop_series_every: int = 1,
@@ -255,7 +256,8 @@ class BatchedEngine:
                 energy_budget_j=energy_budget_j, agent=rl_agent,
                 fused_critic=bool(rl_fused_critic),
                 fused_critic_mlp=bool(rl_fused_critic_mlp),
-                fused_optim=bool(rl_fused_optim))
+                fused_optim=bool(rl_fused_optim),
+                fused_actor_heads=bool(rl_fused_actor_heads))
             serve_device, mfma_serve = rl_loop.serving_mode(
                 self.rl, obs_dim, n_dc, n_g, RL_HID, rl_serve,
                 bool(rl_deterministic))

@@ -50,7 +50,7 @@ def pace_train(backlog, n_new, replay_size, interval, world, gate):
 def make_learner(obs_dim, n_dc, n_g, device, *, world, seed, buffer,
                  sla_p99_ms, power_cap=0.0, energy_budget_j=None, agent=None,
                  fused_critic=False, fused_critic_mlp=False,
-                 fused_optim=False):
+                 fused_optim=False, fused_actor_heads=False):
     """The CHSAC-AF agent (unless one is injected) and its replay ring, both
     on ``device``."""
     if agent is None:
@@ -64,7 +64,8 @@ def make_learner(obs_dim, n_dc, n_g, device, *, world, seed, buffer,
             obs_dim=obs_dim, n_dc=n_dc, n_g_choices=n_g,
             constraints=constraints, device=str(device),
             graph_capturable=(world == 1), fused_critic=fused_critic,
-            fused_critic_mlp=fused_critic_mlp, fused_optim=fused_optim))
+            fused_critic_mlp=fused_critic_mlp, fused_optim=fused_optim,
+            fused_actor_heads=fused_actor_heads))
     replay = ReplayRing(capacity=int(buffer), obs_dim=obs_dim, n_costs=3,
                         cost_names=COST_NAMES, n_dc=n_dc, n_g=n_g,
                         device=str(device), seed=seed)

@@ -38,6 +38,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "actor_heads.hpp"
 #include "arrival_ring.hpp"
 #include "critic_mlp.hpp"
 #include "engine_bind.hpp"
@@ -2879,6 +2880,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weights"), py::arg("h"), py::arg("a_dc"), py::arg("a_g"),
         py::arg("n_dc"), py::arg("n_g"), py::arg("act"), py::arg("dq1"),
         py::arg("dq2"), py::arg("want_dh"), py::arg("want_dw"));
+  m.def("actor_heads_fwd", &dcg::actor_heads_fwd,
+        "both policy heads, the masked Gumbel-max draws and what the backward "
+        "needs (weights[8] = (weight, bias) of head_dc x2, head_g x2; h[B,H]; "
+        "mask_dc, mask_g bool or None; u_dc, u_g uniforms) -> (a_dc[B] i64, "
+        "a_g[B] i64, logp[2,B] per head, act[2,B,H], lp_all[2,B,16])",
+        py::arg("weights"), py::arg("h"), py::arg("mask_dc"),
+        py::arg("mask_g"), py::arg("u_dc"), py::arg("u_g"));
+  m.def("actor_heads_bwd", &dcg::actor_heads_bwd,
+        "policy heads backward (weights[8], h, a_dc, a_g, act, lp_all, "
+        "g[B] = dL/dlogp, want_dh, want_dw) -> (dh[B,H] or None, grads[8] in "
+        "the order of weights, or [], dlogits[2,B,16])",
+        py::arg("weights"), py::arg("h"), py::arg("a_dc"), py::arg("a_g"),
+        py::arg("act"), py::arg("lp_all"), py::arg("g"), py::arg("want_dh"),
+        py::arg("want_dw"));
   m.def("optim_tail", &dcg::optim_tail,
         "fused clip_grad_norm_ + Adam step + polyak over up to 32 f32 tensors "
         "in two launches, in place (params, grads, exp_avgs, exp_avg_sqs, "

@@ -38,6 +38,7 @@ class CHSACAgentConfig:
     fused_critic: bool = False  # HIP kernels for the critic phase (rl/fused.py)
     fused_critic_mlp: bool = False  # HIP twin critic, forward and backward
     fused_optim: bool = False  # HIP clip + Adam + polyak (fused.optim_step)
+    fused_actor_heads: bool = False  # HIP policy heads, draw and backward
 
 
 class CHSACAgent:
@@ -55,7 +56,8 @@ class CHSACAgent:
                                     capturable=cfg.graph_capturable,
                                     fused_critic=cfg.fused_critic,
                                     fused_critic_mlp=cfg.fused_critic_mlp,
-                                    fused_optim=cfg.fused_optim)
+                                    fused_optim=cfg.fused_optim,
+                                    fused_actor_heads=cfg.fused_actor_heads)
         self.cmdp = PIDLagrangian(
             {k: Constraint(name=k, target=v) for k, v in cfg.constraints.items()},
             device=cfg.device)

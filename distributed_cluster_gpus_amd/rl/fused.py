@@ -22,6 +22,13 @@ that is launched only when the critic's parameters ask for gradients.
 ``clip_grad_norm_`` + ``Adam.step()`` of each optimizer, and the polyak
 average of the target critic, by ``optim_step``: two launches of
 ops/csrc/hip/optim_tail.hpp per optimizer, on torch's own Adam state.
+
+``MaskedHybridSAC(fused_actor_heads=True)`` (independent of the three) runs
+the two policy heads of the actor phase in HIP (ops/csrc/hip/
+actor_heads.hpp): ``actor_heads`` is an autograd Function over a forward
+kernel that also draws the masked Gumbel-max actions, a backward kernel that
+starts from the closed-form gradient of the chosen log-prob, and a
+weight-gradient kernel launched only when a head parameter asks for one.
 """
 from typing import List, Optional
 
@@ -55,6 +62,12 @@ def critic_linears(critic) -> List[nn.Linear]:
     """The 6 Linear layers of a twin critic, in the kernels' order."""
     return [critic.q1[0], critic.q1[2], critic.q1[4],
             critic.q2[0], critic.q2[2], critic.q2[4]]
+
+
+def head_linears(actor) -> List[nn.Linear]:
+    """The 4 Linear layers of the two policy heads, in the kernels' order."""
+    return [actor.head_dc[0], actor.head_dc[2],
+            actor.head_g[0], actor.head_g[2]]
 
 
 def unusable(algo, entry: str = "sac_td_target") -> Optional[str]:
@@ -175,6 +188,56 @@ def twin_critic(critic, h, a_dc, a_g, weight_grads: bool):
     return _TwinCritic.apply(h.float().contiguous(), a_dc.long().contiguous(),
                              a_g.long().contiguous(), critic.n_dc, critic.n_g,
                              *weights)
+
+
+class _ActorHeads(torch.autograd.Function):
+    """(h, mask_dc, mask_g, u_dc, u_g, *weights[8]) -> (a_dc, a_g, logp).  The
+    actions carry no gradient.  The backward computes only what autograd asks
+    for: dh if h needs a gradient, the eight weight and bias gradients if any
+    head parameter does."""
+
+    @staticmethod
+    def forward(ctx, h, mask_dc, mask_g, u_dc, u_g, *weights):
+        a_dc, a_g, logp2, act, lp_all = _mod().actor_heads_fwd(
+            list(weights), h, mask_dc, mask_g, u_dc, u_g)
+        ctx.save_for_backward(h, a_dc, a_g, act, lp_all, *weights)
+        ctx.mark_non_differentiable(a_dc, a_g)
+        return a_dc, a_g, logp2[0] + logp2[1]
+
+    @staticmethod
+    def backward(ctx, _da_dc, _da_g, g):
+        h, a_dc, a_g, act, lp_all, *weights = ctx.saved_tensors
+        want_dh = ctx.needs_input_grad[0]
+        want_dw = any(ctx.needs_input_grad[5:])
+        dh, grads, _ = _mod().actor_heads_bwd(
+            weights, h, a_dc, a_g, act, lp_all, g.contiguous(), want_dh,
+            want_dw)
+        return (dh, None, None, None, None, *(grads or [None] * 8))
+
+
+def actor_heads_from_uniforms(actor, h, mask_dc, mask_g, u_dc, u_g):
+    """``actor_heads`` on given uniforms ``u_dc [B, n_dc]``, ``u_g [B, n_g]``
+    instead of fresh draws from the device generator."""
+    def m(mask):
+        return None if mask is None else mask.bool().contiguous()
+    weights = []
+    for lin in head_linears(actor):
+        weights += [lin.weight, lin.bias]
+    return _ActorHeads.apply(h.float().contiguous(), m(mask_dc), m(mask_g),
+                             u_dc, u_g, *weights)
+
+
+def actor_heads(actor, h, mask_dc, mask_g):
+    """``actor(h)`` and the two ``sample_categorical`` draws on the HIP
+    kernels of ops/csrc/hip/actor_heads.hpp: returns ``(a_dc, a_g, logp)``
+    with ``logp = logp_dc + logp_g`` differentiable in ``h`` and in the eight
+    head parameters.  Draws u_dc then u_g exactly as the two ``rand_like``
+    calls of the torch path do, so both consume the device generator alike.
+    A row whose mask allows no action is not supported."""
+    B = h.shape[0]
+    u_dc = torch.rand(B, actor.n_dc, device=h.device)
+    u_g = torch.rand(B, actor.n_g, device=h.device)
+    return actor_heads_from_uniforms(actor, h, mask_dc, mask_g, u_dc, u_g)
 
 
 # optim_tail's table limit (TORCH_CHECKed again before any launch)

@@ -48,7 +48,7 @@ class MaskedHybridSAC(nn.Module):
                  alpha: float = 0.2, actor_lr: float = 3e-4, critic_lr: float = 3e-4,
                  device: Optional[torch.device] = None, capturable: bool = False,
                  fused_critic: bool = False, fused_critic_mlp: bool = False,
-                 fused_optim: bool = False):
+                 fused_optim: bool = False, fused_actor_heads: bool = False):
         super().__init__()
         self.encoder, self.actor, self.critic = encoder, actor, critic
         self.target_critic = TwinQuantileCritic(encoder.out_dim, actor.n_dc,
@@ -86,6 +86,22 @@ class MaskedHybridSAC(nn.Module):
         # flags above, same decide-once and fallback rule
         self.fused_optim = bool(fused_optim)
         self._fused_optim_ready: Optional[bool] = None
+        # opt-in HIP policy heads in the actor phase (fused.actor_heads):
+        # forward, masked draws and backward; independent of the three flags
+        # above, same decide-once and fallback rule
+        self.fused_actor_heads = bool(fused_actor_heads)
+        self._fused_heads_ready: Optional[bool] = None
+
+    def _use_fused_heads(self) -> bool:
+        if not self.fused_actor_heads:
+            return False
+        if self._fused_heads_ready is None:
+            why = fused.unusable(self, "actor_heads_fwd")
+            if why is not None:
+                warnings.warn(f"fused_actor_heads unavailable: {why}; "
+                              "falling back to the torch policy heads")
+            self._fused_heads_ready = why is None
+        return self._fused_heads_ready
 
     def _use_fused_optim(self) -> bool:
         if not self.fused_optim:
@@ -216,10 +232,14 @@ class MaskedHybridSAC(nn.Module):
         """-Q + alpha*logp actor loss joint with the learned-temperature
         objective (one backward over both)."""
         h_pi = self.encoder(s)
-        logits_dc, logits_g = self.actor(h_pi)
-        a_dc_pi, logp_dc = sample_categorical(logits_dc, mask_dc)
-        a_g_pi, logp_g = sample_categorical(logits_g, mask_g)
-        logp = logp_dc + logp_g
+        if self._use_fused_heads():
+            a_dc_pi, a_g_pi, logp = fused.actor_heads(self.actor, h_pi,
+                                                      mask_dc, mask_g)
+        else:
+            logits_dc, logits_g = self.actor(h_pi)
+            a_dc_pi, logp_dc = sample_categorical(logits_dc, mask_dc)
+            a_g_pi, logp_g = sample_categorical(logits_g, mask_g)
+            logp = logp_dc + logp_g
         # no critic weight gradients here: actor_opt holds no critic parameter
         # and the next critic_opt.zero_grad drops them unread
         q1_pi, q2_pi = self._q(h_pi, a_dc_pi, a_g_pi, False)

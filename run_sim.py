@@ -156,6 +156,12 @@ def parse_args(argv=None):
                         "and polyak of each SAC optimizer step as two HIP "
                         "kernels (falls back to torch with a warning if they "
                         "cannot serve the agent).")
+    p.add_argument("--rl-fused-actor-heads", action="store_true",
+                   default=False,
+                   help="chsac_af batched engine: run the two policy heads, "
+                        "the masked draws and their backward in the SAC actor "
+                        "phase as HIP kernels (falls back to torch with a "
+                        "warning if they cannot serve the agent).")
     p.add_argument("--rl-fused-critic", action="store_true", default=False,
                    help="chsac_af batched engine: run the SAC critic phase's "
                         "TD target and quantile-Huber loss as fused HIP "
@@ -298,6 +304,7 @@ def main(argv=None):
                             rl_fused_critic=args.rl_fused_critic,
                             rl_fused_critic_mlp=args.rl_fused_critic_mlp,
                             rl_fused_optim=args.rl_fused_optim,
+                            rl_fused_actor_heads=args.rl_fused_actor_heads,
                             fp32_coeff_eval=args.fp32_coeff_eval,
                             pop_series=args.pop_series > 0,
                             pop_series_every=max(1, args.pop_series),

@@ -1,7 +1,8 @@
 """Graph-replayed SAC step rate with the fused critic phase off ("off"), on
 ("on") and on together with the HIP twin critic ("mlp": fused_critic +
 fused_critic_mlp) and with the fused optimizer tail on top ("opt": mlp +
-fused_optim), and the isolated time of each fused kernel against the
+fused_optim) and the HIP policy heads on top of that ("heads": opt +
+fused_actor_heads), and the isolated time of each fused kernel against the
 torch code it replaces.
 
 Same agent, ring and batch as bench.py::measure_rl_steps_per_sec.  All
@@ -13,7 +14,7 @@ hits all alike; the spread printed is min..max over the windows.
 
 Prints one JSON line.  For per-step kernel counts run it once per mode under
 ``rocprofv3 --kernel-trace --stats -- python scripts/gpu_sac_step_perf.py
---only off|on|mlp|opt --repeats 1`` and divide the call counts by the replays."""
+--only off|on|mlp|opt|heads --repeats 1`` and divide the call counts by the replays."""
 import argparse
 import json
 import os
@@ -33,16 +34,18 @@ from distributed_cluster_gpus_amd.rl.replay import ReplayRing  # noqa: E402
 from distributed_cluster_gpus_amd.rl.sac import quantile_huber_loss  # noqa: E402
 
 OBS, BATCH = 49, 256
-MODES = ("off", "on", "mlp", "opt")
+MODES = ("off", "on", "mlp", "opt", "heads")
 
 
-def make_stepper(fused_critic, fused_critic_mlp=False, fused_optim=False):
+def make_stepper(fused_critic, fused_critic_mlp=False, fused_optim=False,
+                 fused_actor_heads=False):
     torch.manual_seed(0)
     agent = CHSACAgent(CHSACAgentConfig(
         obs_dim=OBS, n_dc=8, n_g_choices=8,
         constraints={"latency_p99": 500.0, "gpu_over": 0.0}, device="cuda",
         graph_capturable=True, fused_critic=fused_critic,
-        fused_critic_mlp=fused_critic_mlp, fused_optim=fused_optim))
+        fused_critic_mlp=fused_critic_mlp, fused_optim=fused_optim,
+        fused_actor_heads=fused_actor_heads))
     ring = ReplayRing(capacity=4096, obs_dim=OBS, n_costs=2,
                       cost_names=["latency_p99", "gpu_over"], n_dc=8, n_g=8,
                       device="cuda", seed=0)
@@ -60,6 +63,8 @@ def make_stepper(fused_critic, fused_critic_mlp=False, fused_optim=False):
         raise RuntimeError("the HIP twin critic fell back to torch")
     if fused_optim and not agent.algo._fused_optim_ready:
         raise RuntimeError("the fused optimizer tail fell back to torch")
+    if fused_actor_heads and not agent.algo._fused_heads_ready:
+        raise RuntimeError("the HIP policy heads fell back to torch")
     return step
 
 
@@ -123,7 +128,7 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--repeats", type=int, default=7)
     p.add_argument("--only", default=None,
-                   help="comma-separated subset of off,on,mlp,opt")
+                   help="comma-separated subset of off,on,mlp,opt,heads")
     args = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -131,7 +136,8 @@ def main(argv=None):
     if not set(only) <= set(MODES):
         raise SystemExit(f"--only takes a subset of {','.join(MODES)}")
     modes = [m for m in MODES if m in only]
-    steppers = {m: make_stepper(m != "off", m in ("mlp", "opt"), m == "opt")
+    steppers = {m: make_stepper(m != "off", m in ("mlp", "opt", "heads"),
+                                m in ("opt", "heads"), m == "heads")
                 for m in modes}
     for s in steppers.values():
         window(s, args.warmup)
@@ -155,6 +161,10 @@ def main(argv=None):
         out["speedup_opt_over_mlp_median"] = round(
             out["steps_per_s_opt"]["median"] /
             out["steps_per_s_mlp"]["median"], 3)
+    if "opt" in modes and "heads" in modes:
+        out["speedup_heads_over_opt_median"] = round(
+            out["steps_per_s_heads"]["median"] /
+            out["steps_per_s_opt"]["median"], 3)
     if args.only is None:
         out.update({k: round(v, 1) for k, v in
                     isolated(steppers["on"].agent.algo).items()})

@@ -39,6 +39,8 @@ def main(argv=None):
                    help="HIP kernels for the twin critic's forward and backward")
     p.add_argument("--fused-optim", action="store_true", default=False,
                    help="HIP kernels for gradient clip, Adam step and polyak")
+    p.add_argument("--fused-actor-heads", action="store_true", default=False,
+                   help="HIP kernels for the policy heads, draws and backward")
     p.add_argument("--checkpoint", type=str, default="chsac_dp.pt")
     p.add_argument("--replay-npz", type=str, default=None,
                    help="also dump the replay ring as an offline .npz dataset")
@@ -69,7 +71,8 @@ def main(argv=None):
                         rl_train_interval=args.train_interval,
                         rl_fused_critic=args.fused_critic,
                         rl_fused_critic_mlp=args.fused_critic_mlp,
-                        rl_fused_optim=args.fused_optim)
+                        rl_fused_optim=args.fused_optim,
+                        rl_fused_actor_heads=args.fused_actor_heads)
     # replicate the agent across ranks, then train data-parallel
     for mod in (eng.rl.encoder, eng.rl.actor, eng.rl.critic,
                 eng.rl.algo.target_critic):
